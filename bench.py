@@ -13,6 +13,11 @@ last step has been queued; fields never leave HBM.  Independent realisations go 
 --streams boxes on their own HIP streams (default 2), so that the arithmetic-bound generator /
 binning passes of one realisation run beside the memory-bound passes of another.
 
+--steps K is the number of timed steps: K in all, as up to --regions fenced regions of >= 200 steps
+each (one region below 400); `ms_per_step` is the median region's time per step.  Before them the realisation counters are
+rewound, so that the timed steps draw the same inputs on every run; --dump-outputs DIR then writes
+what the last one returned (spectrum and delta_x, see dump_outputs) for output-for-output comparisons.
+
 `python bench.py --gpus N` starts N ranks by itself (torch.distributed.run, one per GPU, RCCL) unless it
 is already running under a launcher (WORLD_SIZE set).  Every rank runs independent realisations of the
 same box (Monte-Carlo replicas, no data-path collective; "scaling": "weak"); `value` is the whole-job rate.
@@ -44,6 +49,9 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0      # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
+REGION_MIN_STEPS = 200    # a fenced region drains the pipeline of queued steps once (~0.4 ms at 512^3): no shorter region
+DUMP_VOXELS = 1 << 22      # --dump-outputs: delta_x voxels written at most (16 MB in fp32, 32 MB in fp64)
+DUMP_SEED = 20240601       # --dump-outputs: the sample of delta_x voxels of a larger box
 
 
 def parse(argv=None):
@@ -80,8 +88,10 @@ def parse(argv=None):
                          "raises its clocks over ~50 ms of load (tools/step_timeline.py: the first 20 steps after an idle "
                          "gap run 10 %% below the sustained rate), and the metric is the sustained rate")
     ap.add_argument("--regions", type=int, default=5,
-                    help="timed regions of --steps steps each, back to back (each bracketed by barrier + synchronize on both "
-                         "sides, max over ranks); the headline is the MEDIAN region, every region's time is listed")
+                    help="the --steps timed steps run as this many back-to-back regions, fewer where a region would hold "
+                         "less than %d steps (sizes differ by at most one step; each bracketed by barrier + synchronize on "
+                         "both sides, max over ranks); the headline is the MEDIAN region's time per step, every region's "
+                         "is listed" % REGION_MIN_STEPS)
     ap.add_argument("--plane-batch", type=int, default=None,
                     help="x-planes per cache-resident batch of the y/z passes (default: the library's size for one box per "
                          "GPU when --streams 1, N/8 when several boxes share the GPU)")
@@ -98,7 +108,16 @@ def parse(argv=None):
                          "the timed region (an event pair costs ~3 us of stream time)")
     ap.add_argument("--all-kernel-events", action="store_true",
                     help="--streams 1: bracket every kernel with HIP events (per-kernel breakdown; costs ~4 %% of the rate)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one returned to its caller as DIR/<name>.npy: the "
+                         "spectrum (pk_k, pk, pk_stddev; bins without modes left out) and delta_x (whole up to %d voxels, else a fixed seeded sample of "
+                         "that many)" % DUMP_VOXELS)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps: at least one timed step")
+    if args.dump_outputs is not None and args.mode != "replicas":
+        ap.error("--dump-outputs: --mode replicas only")
+    return args
 
 
 def _free_port():
@@ -276,10 +295,57 @@ def _step_fn(boxes, nbins, lognormal=True, keep_field=True):
     def step():
         box = boxes[counter[0] % len(boxes)]
         counter[0] += 1
+        step.last_box = box
         dx = box.realise_density()
         return box.binned_power_spectrum(delta_x=box.lognormal(dx) if lognormal else dx, nbins=nbins, wait=False,
                                          keep_field=keep_field)
+
+    def rewind():
+        """The next step runs on the first box, and every box draws from its realisation 0 again: what the steps after
+        this compute does not depend on how many (time-limited) spin-up steps ran before."""
+        counter[0] = 0
+        for b in boxes:
+            b._realisation = 0
+    step.last_box = None
+    step.rewind = rewind
     return step
+
+
+def dump_outputs(out_dir, box, spectrum):
+    """What the caller of the last timed step received: the spectrum triple on the bins that hold modes (an empty bin is
+    NaN, as in the reference; which bins are empty follows from the grid and the bin edges alone) and delta_x (the box's
+    field, in the plan's precision; above DUMP_VOXELS voxels a sample at fixed seeded positions, fetched one x-plane at a
+    time).  Every array written is finite."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    kc, pk, err = (np.asarray(a, dtype=np.float64) for a in spectrum)
+    filled = ~np.isnan(pk)
+    eng, field = box.engine, box.delta_x
+    N = box.N
+    nvox = N ** 3
+    if nvox <= DUMP_VOXELS:
+        dx = np.stack([eng.download_plane(field, ix) for ix in range(N)])
+        idx = None
+    else:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(nvox, size=DUMP_VOXELS, replace=False))
+        plane = idx // (N * N)
+        dx = np.empty(idx.size, dtype=eng.rdtype)
+        lo = np.searchsorted(plane, np.arange(N + 1))
+        for ix in range(N):
+            if lo[ix + 1] > lo[ix]:
+                dx[lo[ix]:lo[ix + 1]] = eng.download_plane(field, ix).reshape(-1)[idx[lo[ix]:lo[ix + 1]] - ix * N * N]
+    arrays = {"pk_k": kc[filled], "pk": pk[filled], "pk_stddev": err[filled], "delta_x": dx}
+    for name, a in arrays.items():
+        if not np.all(np.isfinite(a)):
+            raise FloatingPointError("--dump-outputs: %s is not finite" % name)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": os.path.abspath(out_dir), "files": sorted(n + ".npy" for n in arrays),
+            "bytes": int(sum(a.nbytes for a in arrays.values())), "realisation": getattr(box, "last_realisation", None),
+            "seed": box.seed, "empty_bins_left_out": [int(i) for i in np.nonzero(~filled)[0]],
+            "delta_x": "whole field" if idx is None else
+            "%d of %d voxels in flat index order, positions np.random.default_rng(%d).choice(%d, %d, replace=False) sorted"
+            % (idx.size, nvox, DUMP_SEED, nvox, idx.size)}
 
 
 def _check_finite(triples, what):
@@ -552,15 +618,17 @@ def main():
         spin_steps += 10
     _warm(step, max(args.warmup, len(boxes)))
     fence()
+    step.rewind()                         # the timed steps draw the same realisations whatever the spin-up ran
     if in_region:
         eng.profile_start(None if args.all_kernel_events else ["fft_strided"], stride=ev_stride)
-    # the metric is the sustained rate -- the median of `regions` back-to-back regions of exactly K steps, each
-    # fenced (barrier + synchronize) on both sides; `steps` / `ms_per_step` describe ONE region (the median one)
-    nreg = max(1, args.regions)
+    # the metric is the sustained rate -- exactly `steps` timed steps, in `regions` back-to-back regions, each
+    # fenced (barrier + synchronize) on both sides; `ms_per_step` is the median region's time per step
+    nreg = max(1, min(args.regions, args.steps // REGION_MIN_STEPS))
+    sizes = [args.steps // nreg + (1 if i < args.steps % nreg else 0) for i in range(nreg)]
     dts, spectra = [], []
-    for _ in range(nreg):
+    for n_reg in sizes:
         t0 = time.perf_counter()
-        pending = [step() for _ in range(args.steps)]
+        pending = [step() for _ in range(n_reg)]
         spectra += [pnd.result() for pnd in pending]
         if in_region and len(dts) == nreg - 1:
             prof = eng.profile_stop()                    # synchronises the launch stream
@@ -568,9 +636,12 @@ def main():
         fence()
         dts.append(time.perf_counter() - t0)
     if in_region:
-        prof_steps = args.steps * nreg
+        prof_steps = args.steps
     gc.enable()
     _check_finite(spectra, "timed region")       # every rank: a rank that timed garbage stops the job
+    dumped = None
+    if args.dump_outputs is not None and rank == 0:
+        dumped = dump_outputs(args.dump_outputs, step.last_box, spectra[-1])
     ln_repeats = sum(getattr(b, "lognormal_repeats", 0) for b in boxes)
     collective = None
     if world > 1:
@@ -580,7 +651,8 @@ def main():
         collective = _collective_info(torch, dist, local_rank)
         dist.barrier()
         dist.destroy_process_group()
-    dt = sorted(dts)[len(dts) // 2]
+    per_step = sorted(d / n for d, n in zip(dts, sizes))
+    dt = per_step[len(per_step) // 2]                # seconds per step of the median region
     if rank != 0:
         return
 
@@ -600,15 +672,16 @@ def main():
     line = {
         "metric": "%d^3 box realisations/sec (gen + log-normal + P(k))" % N if not args.gaussian_only
                   else "%d^3 box realisations/sec (gen + P(k), NO log-normal: tuning run)" % N,
-        "value": world * args.steps / dt, "unit": "boxes/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "higher_is_better": True,
+        "value": world / dt, "unit": "boxes/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": 1e3 * dt, "higher_is_better": True,
         "scaling": "weak", "vs_baseline": None, "dtype": args.precision, "data": "synthetic",
         "finite": True, "lognormal_repeats": ln_repeats,
-        "regions": {"count": len(dts), "ms_per_step": [round(1e3 * d / args.steps, 5) for d in dts],
-                    "boxes_per_s": [round(world * args.steps / d, 2) for d in dts],
-                    "spread": (max(dts) - min(dts)) / dt,
-                    "what": "back-to-back timed regions of `steps` steps, each fenced on both sides (max over ranks per "
+        "regions": {"count": len(dts), "steps": sizes, "ms_per_step": [round(1e3 * d / n, 5) for d, n in zip(dts, sizes)],
+                    "boxes_per_s": [round(world * n / d, 2) for d, n in zip(dts, sizes)],
+                    "spread": (per_step[-1] - per_step[0]) / dt,
+                    "what": "the `steps` timed steps as back-to-back regions, each fenced on both sides (max over ranks per "
                             "region); value / ms_per_step are the MEDIAN region's"},
+        "dump_outputs": dumped,
         "collective": collective,
         "config": {"workload": "%d^3 Gaussian box (device Philox4x32-10 noise, stand-in EH P(k), L=1000 Mpc) + "
                                "log-normal transform + binned P(k), nbins=%d" % (N, args.nbins),

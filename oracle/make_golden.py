@@ -44,6 +44,13 @@ CASES = [
 ]
 
 
+# whole fields (no probe stride) and one spectrum of a grid size the cases above do not use
+# (tests/test_oracle.py::test_oracle_against_reference_n24): (name, nsamp, box_scale, seed, nbins)
+FULL_CASES = [
+    ("ref_n24_l300", 24, (3e2, 3e2, 3e2), 5, 30),
+]
+
+
 ONLY = set(sys.argv[1:])          # python -m oracle.make_golden [case ...]: default all
 
 
@@ -138,12 +145,30 @@ def capture(ref, name, N, box_scale, redshift, seed, s, what):
     print("wrote", name, "(%d arrays)" % len(out))
 
 
+def capture_full(ref, name, N, box_scale, seed, nbins):
+    np.random.seed(seed)
+    box = ref.CosmoBox(cosmo=standin.DEFAULT_COSMO, box_scale=box_scale, nsamp=N, realise_now=False)
+    box.realise_density()
+    import warnings
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        kc, pk, err = box.binned_power_spectrum(nbins=nbins)
+    out = dict(numpy_version=np.__version__, scipy_version=scipy.__version__,
+               N=N, box_scale=np.atleast_1d(np.asarray(box_scale, dtype=np.float64)), seed=seed, nbins=nbins,
+               delta_x=box.delta_x, delta_k=box.delta_k, pk_k=kc, pk_p=pk, pk_e=err)
+    np.savez_compressed(os.path.join(OUT, name + ".npz"), **out)
+    print("wrote", name, "(%d arrays)" % len(out))
+
+
 def main():
     ref = load_reference_box()
     os.makedirs(OUT, exist_ok=True)
     for case in CASES:
         if not ONLY or case[0] in ONLY:
             capture(ref, *case)
+    for case in FULL_CASES:
+        if not ONLY or case[0] in ONLY:
+            capture_full(ref, *case)
 
 
 if __name__ == "__main__":

@@ -22,7 +22,7 @@ def _json_lines(text):
 
 
 def test_single_gpu_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "6", "--warmup", "2", "--nsamp", "256",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1000", "--warmup", "2", "--nsamp", "256",
                         "--cpu-nsamp", "64", "--sizes", "128,512"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = _json_lines(r.stdout)
@@ -31,7 +31,7 @@ def test_single_gpu_line():
     for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling",
                 "vs_baseline", "dtype", "data", "config", "roofline", "cpu_baseline"):
         assert key in d, key
-    assert d["n_gpus"] == 1 and d["steps"] == 6 and d["warmup"] == 2 and d["higher_is_better"] is True
+    assert d["n_gpus"] == 1 and d["steps"] == 1000 and d["warmup"] == 2 and d["higher_is_better"] is True
     assert d["unit"] == "boxes/s" and d["value"] > 0 and d["vs_baseline"] is None and d["scaling"] == "weak"
     assert abs(d["ms_per_step"] * d["value"] - 1e3) < 1e-6 * 1e3
     assert "workload" in d["config"] and "model" not in d["config"]
@@ -50,9 +50,10 @@ def test_single_gpu_line():
     pr = d["pipeline_roofline"]
     assert pr["model_sweeps"] == 5.0 and pr["moved_sweeps"] == 4.5 and 0 < pr["frac_moved"] < pr["frac"] < 1
     assert "from_profiles" in d and "file" in d["from_profiles"] and "head" in d["from_profiles"]
-    # the headline is the median of >= 5 fenced regions of `steps` steps, every region listed
+    # the headline is the median of >= 5 fenced regions that hold the `steps` timed steps, every region listed
     rg = d["regions"]
     assert rg["count"] >= 5 and len(rg["ms_per_step"]) == rg["count"] and all(x > 0 for x in rg["ms_per_step"])
+    assert len(rg["steps"]) == rg["count"] and sum(rg["steps"]) == d["steps"]
     assert sorted(rg["ms_per_step"])[rg["count"] // 2] == pytest.approx(d["ms_per_step"], rel=1e-3) and rg["spread"] >= 0
     assert d["collective"] is None                 # one rank: no process group
     assert "best of" in c3["workload"]
@@ -64,7 +65,7 @@ def test_two_ranks_started_by_bench_itself():
     as a child job of two ranks."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(FASTBOX_BENCH_BACKEND="gloo", FASTBOX_BENCH_ONE_DEVICE="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "6", "--warmup", "2",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1000", "--warmup", "2",
                         "--nsamp", "128", "--slab-sizes", "64"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
@@ -79,7 +80,7 @@ def test_two_ranks_started_by_bench_itself():
         assert c["backend"] == "gloo" and c["world_size"] == 2 and len(c["devices"]) == 2
         assert sorted(g["rank"] for g in c["devices"]) == [0, 1] and all("device" in g and "pci_bus_id" in g for g in c["devices"])
     group_ok(d["collective"])
-    assert d["regions"]["count"] >= 5
+    assert d["regions"]["count"] >= 5 and sum(d["regions"]["steps"]) == d["steps"] == 1000
     ss = d["strong_scaling"]["64"]
     assert ss["n_gpus"] == 2 and ss["scaling"] == "strong" and math.isfinite(ss["value"]) and ss["value"] > 0
     assert math.isfinite(ss["ms_per_step"]) and ss["finite"] is True
@@ -101,3 +102,46 @@ def test_two_ranks_under_an_external_launcher():
     lines = _json_lines(r.stdout)
     assert len(lines) == 1 and lines[0]["n_gpus"] == 2 and lines[0]["value"] > 0
     assert lines[0]["collective"]["world_size"] == 2 and lines[0]["collective"]["backend"] == "gloo"
+
+
+def test_dump_outputs_are_the_last_timed_step_and_repeat_run_for_run(tmp_path):
+    """--dump-outputs: the last timed step's spectrum and (a seeded sample of) its delta_x, the same files whatever the
+    spin-up ran, and the same numbers as the public API gives for the realisation the line names."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    N, steps = 256, 30
+    runs = []
+    for i, spin in enumerate(("0", "0.3")):
+        out = tmp_path / ("run%d" % i)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(steps), "--warmup", "2",
+                            "--nsamp", str(N), "--no-extras", "--no-cpu-baseline", "--spin-up", spin,
+                            "--dump-outputs", str(out)], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = _json_lines(r.stdout)
+        assert len(lines) == 1 and lines[0]["steps"] == steps
+        info = lines[0]["dump_outputs"]
+        names = sorted(os.listdir(str(out)))
+        assert names == sorted(info["files"]) == ["delta_x.npy", "pk.npy", "pk_k.npy", "pk_stddev.npy"]
+        assert sum(os.path.getsize(str(out / n)) for n in names) <= 64 << 20
+        runs.append((info, {n[:-4]: np.load(str(out / n)) for n in names}))
+    (info, got), (info2, got2) = runs
+    assert info["seed"] == info2["seed"] and info["realisation"] == info2["realisation"]
+    for name, a in got.items():
+        assert a.dtype in (np.float32, np.float64) and np.all(np.isfinite(a)), name
+        assert np.array_equal(a, got2[name], equal_nan=True), name
+    assert got["delta_x"].dtype == np.float32 and got["delta_x"].shape == (bench.DUMP_VOXELS,)
+    # the same realisation through the public API
+    from fastbox_amd import CosmoBox, default_cosmo
+    box = CosmoBox(cosmo=default_cosmo, box_scale=1e3, nsamp=N, redshift=0., realise_now=False, precision="f32",
+                   rng="device", seed=info["seed"])
+    box._realisation = info["realisation"]
+    dx = box.realise_density()
+    kc, pk, err = box.binned_power_spectrum(delta_x=box.lognormal(dx), nbins=20)
+    filled = ~np.isnan(pk)                                 # empty bins are NaN in what the caller gets, and left out
+    assert list(np.nonzero(~filled)[0]) == info["empty_bins_left_out"]
+    assert np.array_equal(kc[filled], got["pk_k"]) and np.array_equal(pk[filled], got["pk"])
+    assert np.array_equal(err[filled], got["pk_stddev"])
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).choice(N ** 3, size=bench.DUMP_VOXELS, replace=False))
+    assert np.array_equal(np.asarray(dx).reshape(-1)[idx].astype(np.float32), got["delta_x"])
+    box.engine.close()

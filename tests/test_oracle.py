@@ -123,27 +123,19 @@ def test_oracle_at_the_headline_size(golden_dir):
     assert _same(pk, g["pkln_p"]) and _same(err, g["pkln_e"])
 
 
-def test_oracle_against_live_reference():
-    """When the reference is on this machine, compare directly on a fresh seed."""
-    from oracle import ref_loader
-    if not ref_loader.reference_available():
-        pytest.skip("reference sources not present (GPU box)")
-    ref = ref_loader.load_reference_box()
-    np.random.seed(5)
-    box = ref.CosmoBox(cosmo=standin.DEFAULT_COSMO, box_scale=(3e2, 3e2, 3e2), nsamp=24, realise_now=False)
-    box.realise_density()
-    geo = bo.box_geometry((3e2, 3e2, 3e2), 24)
-    rng = np.random.RandomState(5)
-    re, im = bo.draw_noise(24, rng)
+def test_oracle_against_reference_n24(golden_dir):
+    """Whole fields and a 30-bin spectrum the reference produced on a grid size no other case uses (a seed of its own;
+    tests/golden/ref_n24_l300.npz, oracle/make_golden.py FULL_CASES)."""
+    g = _load(golden_dir, "ref_n24_l300")
+    N = int(g["N"])
+    geo = bo.box_geometry(_scale(g), N)
+    rng = np.random.RandomState(int(g["seed"]))
+    re, im = bo.draw_noise(N, rng)
     dx, dk = bo.realise_density(geo, standin.pk_fn(standin.cosmology(), 1.0), re, im)
-    assert _same(dx, box.delta_x) and _same(dk, box.delta_k)
-    import warnings
-    with warnings.catch_warnings():
-        warnings.simplefilter("ignore")
-        ref_pk = box.binned_power_spectrum(nbins=30)
-    ora_pk = bo.binned_power_spectrum(geo, dk, nbins=30)
-    for a, b in zip(ref_pk, ora_pk):
-        assert _same(a, b)
+    assert _same(dx, g["delta_x"]) and _same(dk, g["delta_k"])
+    ora_pk = bo.binned_power_spectrum(geo, dk, nbins=int(g["nbins"]))
+    for a, key in zip(ora_pk, ("pk_k", "pk_p", "pk_e")):
+        assert _same(a, g[key]), key
 
 
 # ---- noise / foreground steps (SURVEY 8f rank 2): oracle/sky_oracle.py against vectors captured from the reference
