@@ -68,6 +68,10 @@ SIGNATURES = {
     "fb_montecarlo_power": (c_int, [c_void_p, c_u64, c_u64, c_u64, c_int, c_void_p, c_void_p, c_int, c_void_p, c_i64, c_void_p]),
     "fb_power_spectrum_device": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "fb_bin_counts": (c_int, [c_void_p, P_double]),
+    "fb_cross_power_half": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p]),
+    "fb_bin_separation": (c_int, [c_void_p, c_void_p, P_double, c_int, c_int, P_double, c_void_p]),
+    "fb_correlation_function": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, P_double, c_int, c_int,
+                                        P_double, c_void_p]),
     "fb_real_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_void_p]),
     "fb_real_multiply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fb_real_to_complex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -851,6 +851,44 @@ class CosmoBox(object):
         out = (kc,) + _finish_bins(cnt, s1, s2, self.boxfactor, _eps_of(eng))
         return out if wait else _Ready(out)
 
+    # ------------------------------------------------------------ correlation function
+    def correlation_function(self, delta_x=None, second=None, dr=None, rmin=0., rmax=None, rbins=None, poles=None):
+        """Additive: the two-point correlation function of a real field (or the cross-correlation with ``second``), what the
+        reference's examples take from nbodykit as ``FFTCorr(first=mesh, mode='1d', los=[0,0,1], dr=, rmin=, rmax=)``
+        (examples/example_corr_fn.py:38-47; step (6) of the end-to-end notebooks).  Returns ``(r, xi, npairs)``:
+
+            D_a = fftn(d_a - mean(d_a)),  xi(s) = ifftn(conj(D_1) D_2) / N^3   (periodic);
+            s_a = m_a L_a / N (m_a the signed FFT index), mu = s_z / |s| (line of sight z),
+            bin b = [e_b, e_b+1); npairs = cells per bin, r = mean |s| per bin,
+            xi_l = (2l + 1) sum xi(s) L_l(mu) / npairs.
+
+        ``delta_x`` (default ``self.delta_x``) and ``second`` take whatever ``binned_power_spectrum(delta_x=...)`` takes.
+        Edges: ``rbins``, or np.arange(rmin, rmax + dr/2, dr) with dr = min(L)/N, rmax = min(L)/2 by default (N/2 bins); at
+        most 1024 bins, so the defaults fit every grid up to 2048^3 (ValueError beyond).  ``poles``:
+        None -> xi is the monopole, shape (nbins,); a list out of (0, 2, 4) -> shape (len(poles), nbins).  Empty bins are
+        NaN in r and xi.  The box's state (delta_x, stored spectrum, realisation counter, P(k) bins) is left as it was."""
+        N = self.N
+        L = (self.Lx, self.Ly, self.Lz)
+        edges = hostgeom.separation_edges(L, N, dr=dr, rmin=rmin, rmax=rmax, rbins=rbins)
+        ps = hostgeom.check_poles(poles)
+        for name, f in (("delta_x", delta_x), ("second", second)):
+            if f is None:
+                continue
+            if isinstance(f, DeviceArray):
+                if f.engine is not self.engine or f.kind != REAL:
+                    raise ValueError("%s: a real field of this box" % name)
+            elif np.shape(f) != (N, N, N):
+                raise ValueError("%s: expected an array of shape %s, got %s" % (name, (N, N, N), np.shape(f)))
+        if delta_x is None:
+            delta_x = getattr(self, "delta_x", None)
+            if delta_x is None:
+                raise ValueError("no delta_x: realise_density() first, or pass delta_x")
+        d1 = self._as_real(delta_x)
+        d2 = self._as_real(second) if second is not None else None
+        raw = self.engine.correlation(d1, d2, edges, max(ps))
+        r, xi, npairs = hostgeom.finish_correlation(raw, edges.size - 1, ps)
+        return r, (xi[0].copy() if poles is None else xi), npairs
+
     def sigmaR(self, R):
         """RMS of the field smoothed with a top-hat of R Mpc/h, from the binned power
         spectrum (box.py:657-683; scipy's simps is spelled simpson since 1.14)."""

@@ -3,6 +3,7 @@
 #include "fb_plan.h"
 #include <dlfcn.h>
 #include <rccl/rccl.h>           // types and prototypes only: the functions are looked up in a dlopen'ed librccl (fb_comm.inc)
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -69,7 +70,7 @@ template <typename T> int make_twiddles(void** out, int N) {
 
 extern "C" {
 
-int fb_version(void) { return 100; }
+int fb_version(void) { return 101; }
 const char* fb_last_error(void) { return g_last_error.c_str(); }
 
 int fb_device_count(int* count) {
@@ -152,7 +153,7 @@ int fb_plan_destroy(fb_plan* p) {
     (void)fb_comm_destroy(p);
     (void)hipSetDevice(p->device);
     void* ptrs[] = {p->tw, p->axis2, p->ksc, p->kpar, p->zgrid, p->amp_shell, p->amp_sym, p->kperp_tab, p->pca_work, p->bins, p->thr, p->counts,
-                    p->partials, p->scratch, p->bin_partials, p->exp_partials, p->plane_buf};
+                    p->partials, p->scratch, p->bin_partials, p->exp_partials, p->plane_buf, p->sep_edges, p->sep_partials};
     for (void* q : ptrs) if (q) (void)hipFree(q);
     if (p->aux_stream) { (void)hipStreamSynchronize(p->aux_stream); (void)hipStreamDestroy(p->aux_stream); }
     if (p->ev_fork) (void)hipEventDestroy(p->ev_fork);
@@ -485,6 +486,81 @@ int fb_bin_counts(fb_plan* p, double* count) {
     FB_REQUIRE(p->nbins > 0, "bin edges not set");
     for (int q = 0; q < p->nbins; ++q) count[q] = p->counts_host[q];
     return FB_OK;
+}
+
+// ---- two-point correlation function (examples/example_corr_fn.py:38-47, FFTCorr(mode='1d', los=[0,0,1])) ------------
+int fb_cross_power_half(fb_plan* p, const void* half1, const void* half2, void* half_out, double scale, void* stream) {
+    FB_REQUIRE(p && half1 && half_out, "null pointer");
+    FB_USE_DEVICE(p);
+    hipStream_t s = (hipStream_t)stream;
+    return FB_DISPATCH(p, fbi_cross_power_f32(p, half1, half2, half_out, scale, s),
+                       fbi_cross_power_f64(p, half1, half2, half_out, scale, s));
+}
+
+namespace {
+int sep_args(const double* edges, int nbins, int lmax) {
+    FB_REQUIRE(nbins >= 1 && nbins <= FB_MAX_SEP_BINS, "nbins must be in 1..1024");
+    FB_REQUIRE(lmax == 0 || lmax == 2 || lmax == 4, "lmax must be 0, 2 or 4");
+    FB_REQUIRE(edges[0] >= 0.0, "the first edge must be >= 0");
+    for (int q = 1; q <= nbins; ++q) FB_REQUIRE(edges[q] > edges[q - 1], "separation edges must be strictly ascending");
+    return FB_OK;
+}
+int bin_separation(fb_plan* p, const void* real, const double* edges, int nbins, int lmax, double* out_host, hipStream_t s) {
+    const int nl = lmax / 2 + 1;
+    const double elast = edges[nbins];
+    std::vector<double> key(edges, edges + nbins + 1);
+    if (!p->sep_edges) FB_HIP(hipMalloc((void**)&p->sep_edges, (FB_MAX_SEP_BINS + 1) * sizeof(double)));
+    FB_HIP(hipMemcpyAsync(p->sep_edges, key.data(), key.size() * sizeof(double), hipMemcpyHostToDevice, s));
+    const std::vector<double>* geo = nullptr;
+    for (const auto& e : p->sep_geom)
+        if (e.size() == 3 * (size_t)nbins + 1 && std::equal(key.begin(), key.end(), e.begin())) geo = &e;
+    if (!geo) {                    // cells and sum |s| per bin: data independent, once per bin set
+        int r = FB_DISPATCH(p, fbi_sep_bin_f32(p, nullptr, p->sep_edges, elast, nbins, nl, 1, p->scratch, s),
+                            fbi_sep_bin_f64(p, nullptr, p->sep_edges, elast, nbins, nl, 1, p->scratch, s));
+        if (r) return r;
+        std::vector<double> e(key);
+        e.resize(3 * (size_t)nbins + 1);
+        FB_HIP(hipMemcpyAsync(e.data() + nbins + 1, p->scratch, 2 * (size_t)nbins * sizeof(double), hipMemcpyDeviceToHost, s));
+        FB_HIP(hipStreamSynchronize(s));
+        if (p->sep_geom.size() >= 16) p->sep_geom.erase(p->sep_geom.begin());
+        p->sep_geom.push_back(std::move(e));
+        geo = &p->sep_geom.back();
+    }
+    int r = FB_DISPATCH(p, fbi_sep_bin_f32(p, real, p->sep_edges, elast, nbins, nl, 0, p->scratch, s),
+                        fbi_sep_bin_f64(p, real, p->sep_edges, elast, nbins, nl, 0, p->scratch, s));
+    if (r) return r;
+    FB_HIP(hipMemcpyAsync(out_host + 2 * nbins, p->scratch, (size_t)nl * nbins * sizeof(double), hipMemcpyDeviceToHost, s));
+    FB_HIP(hipStreamSynchronize(s));
+    std::copy(geo->begin() + nbins + 1, geo->end(), out_host);
+    return FB_OK;
+}
+}  // namespace
+
+int fb_bin_separation(fb_plan* p, const void* real, const double* edges, int nbins, int lmax, double* out_host, void* stream) {
+    FB_REQUIRE(p && real && edges && out_host, "null pointer");
+    const int r = sep_args(edges, nbins, lmax);
+    if (r) return r;
+    FB_USE_DEVICE(p);
+    return bin_separation(p, real, edges, nbins, lmax, out_host, (hipStream_t)stream);
+}
+
+int fb_correlation_function(fb_plan* p, const void* real1, const void* real2, void* work_half1, void* work_half2,
+                            void* work_real, const double* edges, int nbins, int lmax, double* out_host, void* stream) {
+    FB_REQUIRE(p && real1 && work_half1 && work_real && edges && out_host, "null pointer");
+    FB_REQUIRE(!real2 || work_half2, "a cross-correlation needs work_half2");
+    int r = sep_args(edges, nbins, lmax);
+    if (r) return r;
+    FB_USE_DEVICE(p);
+    hipStream_t s = (hipStream_t)stream;
+    const double n3 = (double)p->N * p->N * p->N;
+    r = FB_DISPATCH(p, fbi_fft_r2c_f32(p, real1, work_half1, 0, s), fbi_fft_r2c_f64(p, real1, work_half1, 0, s));
+    if (!r && real2) r = FB_DISPATCH(p, fbi_fft_r2c_f32(p, real2, work_half2, 0, s), fbi_fft_r2c_f64(p, real2, work_half2, 0, s));
+    // conj(D_1) D_2 / N^6: fb_fft_c2r applies only the scale it is given, so with 1 it returns (1/N^3) sum_x d_1(x) d_2(x + s)
+    if (!r) r = FB_DISPATCH(p, fbi_cross_power_f32(p, work_half1, real2 ? work_half2 : nullptr, work_half1, 1.0 / (n3 * n3), s),
+                            fbi_cross_power_f64(p, work_half1, real2 ? work_half2 : nullptr, work_half1, 1.0 / (n3 * n3), s));
+    if (!r) r = FB_DISPATCH(p, fbi_fft_c2r_f32(p, work_half1, work_real, 1.0, s), fbi_fft_c2r_f64(p, work_half1, work_real, 1.0, s));
+    if (r) return r;
+    return bin_separation(p, work_real, edges, nbins, lmax, out_host, s);
 }
 
 int fb_real_axpby(fb_plan* p, const void* x, const void* y, void* out, double a, double b, double c, void* stream) {

@@ -1536,4 +1536,151 @@ __global__ __launch_bounds__(256) void k_pca_clean(const T* __restrict__ cube, c
     for (int q = 0; q < CPL; ++q) { const int c = lane + 64 * q; if (c < N) out[p * N + c] = (T)(x[q] - rec[q]); }
 }
 
+// ---- two-point correlation function (nbodykit FFTCorr(mode='1d', los=[0,0,1]) on a mesh) ---------------------
+// examples/example_corr_fn.py:38-47 and step (6) of the end-to-end notebooks:
+//   D_a = fftn(delta_a - mean), xi(s) = ifftn(conj(D_1) D_2) / N^3, binned by |s| with multipoles in mu = s_z / |s|.
+// Spectrum product on a half spectrum: out = conj(a) b * scale (b = null: |a|^2, imaginary part exactly 0); the k = 0
+// mode is set to 0 (removing the mean changes that mode only).  out may be a or b (no __restrict__ on them).
+// One flat pass over the stored half spectrum (rows of NZP, N + 1 rows per x-plane): coalesced whatever N / 2 + 1 is;
+// the padding columns and the spare row are neither read nor written.
+template <typename T>
+__global__ __launch_bounds__(256) void k_cross_power(const cx<T>* a, const cx<T>* b, cx<T>* out, KGeom g, double scale) {
+    const unsigned long long n = (unsigned long long)g.N * g.NR * g.NZP;
+    for (unsigned long long q = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; q < n;
+         q += (unsigned long long)gridDim.x * blockDim.x) {
+        const unsigned long long row = q / (unsigned)g.NZP;
+        const int l = (int)(q - row * (unsigned)g.NZP), j = (int)(row % (unsigned)g.NR);
+        if (l >= g.NZV || j >= g.N) continue;
+        const cx<T> d1 = a[q];
+        double re, im;
+        if (b) {
+            const cx<T> d2 = b[q];
+            re = (double)d1.x * d2.x + (double)d1.y * d2.y;
+            im = (double)d1.x * d2.y - (double)d1.y * d2.x;
+        } else {
+            re = (double)d1.x * d1.x + (double)d1.y * d1.y;
+            im = 0.0;
+        }
+        if (q == 0) re = im = 0.0;                                    // k = 0
+        out[q] = cx<T>{(T)(re * scale), (T)(im * scale)};
+    }
+}
+
+// Binning of a real field xi(s) by separation.  s_a = m_a (L_a / N), m_a the signed index (Nyquist negative);
+// |s| = sqrt((s_x s_x + s_y s_y) + s_z s_z) in fp64 without contraction; bin b = np.digitize(|s|, edges) - 1.
+// |s| and mu^2 depend on |m_x|, |m_y|, |m_z| only (the squares of -m h and m h are the same double), and the multipoles
+// are even in mu: a wave takes one (|m_x|, |m_y|) row and folds the up to four z lines of (+-m_x, +-m_y), a lane one
+// |m_z| = t of them (up to eight cells summed in fp64).  Only |m_a| <= M_a (the corner blocks that can reach the last
+// edge) is visited; rows and 64-lane steps that start beyond the last edge stop at once, cells outside the edges are
+// not read.  Along a row |s| grows with t, so the lanes' bins are ascending: a step inside one bin takes plain wave
+// sums (the fast path), otherwise a segmented scan leaves each bin's sum in the last lane of its run, and those lanes
+// (distinct bins) add into the wave's LDS row.  Per-workgroup partials, then k_bin_finish: no atomics, fixed order.
+// GEOM: the data-independent sums (number of cells, sum |s|) instead of sum xi L_l(mu), l = 0, 2, .. 2 (nl - 1).
+struct SepGeom {
+    const double* edges;   // [nbins + 1] ascending
+    int nbins, nl;         // nl = lmax / 2 + 1 multipoles (GEOM: 2 values)
+    int N, M[3];           // largest |m_a| visited per axis
+    double h[3];           // L_a / N
+};
+#define FB_SEP_WAVES 4
+__device__ __forceinline__ double sep_sq(double sx, double sy) {
+#pragma clang fp contract(off)
+    return sx * sx + sy * sy;
+}
+__device__ __forceinline__ double sep_mag(double sxy, double sz) {
+#pragma clang fp contract(off)
+    return sqrt(sxy + sz * sz);
+}
+__device__ __forceinline__ int sep_bin(const double* le, int nb, double r) {     // number of edges <= r, minus 1
+    int lo = 0, hi = nb + 1;
+    while (lo < hi) { const int mid = (lo + hi) >> 1; if (le[mid] <= r) lo = mid + 1; else hi = mid; }
+    return lo - 1;
+}
+template <typename T, bool GEOM>
+__global__ __launch_bounds__(64 * FB_SEP_WAVES)
+void k_sep_bin(const T* __restrict__ xi, double* __restrict__ partial, SepGeom sg) {
+    constexpr int NV = GEOM ? 2 : 3;
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int nb = sg.nbins, nv = GEOM ? 2 : sg.nl, N = sg.N;
+    double* le = reinterpret_cast<double*>(smem);
+    double* acc = le + nb + 1;                                        // [waves][nv][nb]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    for (int q = tid; q <= nb; q += blockDim.x) le[q] = sg.edges[q];
+    for (int q = tid; q < FB_SEP_WAVES * nv * nb; q += blockDim.x) acc[q] = 0.0;
+    __syncthreads();
+    double* row_acc = acc + (size_t)wave * nv * nb;
+    const double elast = le[nb];
+    const long long ny = sg.M[1] + 1, nrows = (long long)(sg.M[0] + 1) * ny;
+    for (long long row = (long long)blockIdx.x * FB_SEP_WAVES + wave; row < nrows;
+         row += (long long)gridDim.x * FB_SEP_WAVES) {
+        const int a = (int)(row / ny), bq = (int)(row % ny);
+        const double sxy = sep_sq((double)a * sg.h[0], (double)bq * sg.h[1]);
+        if (sep_mag(sxy, 0.0) >= elast) continue;                     // the whole row lies beyond the last edge
+        const int i2 = (a == 0 || 2 * a == N) ? -1 : N - a, j2 = (bq == 0 || 2 * bq == N) ? -1 : N - bq;
+        const long long ln[4] = {((long long)a * N + bq) * N, j2 < 0 ? -1 : ((long long)a * N + j2) * N,
+                                 i2 < 0 ? -1 : ((long long)i2 * N + bq) * N,
+                                 (i2 < 0 || j2 < 0) ? -1 : ((long long)i2 * N + j2) * N};
+        const double cxy = (double)((i2 < 0 ? 1 : 2) * (j2 < 0 ? 1 : 2));
+        for (int t0 = 0; t0 <= sg.M[2]; t0 += 64) {
+            const int t = t0 + lane;
+            const bool in = t <= sg.M[2];
+            const double sz = (double)t * sg.h[2];
+            const double r = sep_mag(sxy, sz);
+            if (__shfl(r, 0, 64) >= elast) break;                     // lane 0 (t0) beyond the last edge: so is the rest
+            int b = in ? sep_bin(le, nb, r) : nb + 1;                 // ascending over the lanes
+            const bool ok = b >= 0 && b < nb;
+            const int t2 = (t == 0 || 2 * t == N) ? -1 : N - t;
+            double v[NV];
+            if (GEOM) {
+                const double c = ok ? cxy * (t2 < 0 ? 1.0 : 2.0) : 0.0;
+                v[0] = c; v[1] = c * r;
+            } else {
+                double x = 0.0;
+                if (ok) {
+#pragma unroll
+                    for (int u = 0; u < 4; ++u)
+                        if (ln[u] >= 0) { x += (double)xi[ln[u] + t]; if (t2 >= 0) x += (double)xi[ln[u] + t2]; }
+                }
+                const double mu = r > 0.0 ? sz / r : 0.0, m2 = mu * mu;
+                v[0] = x;
+                v[1] = x * (1.5 * m2 - 0.5);
+                v[2] = x * (((35.0 * m2 - 30.0) * m2 + 3.0) * 0.125);
+            }
+            const int bfirst = __shfl(b, 0, 64), blast = __shfl(b, 63, 64);
+            if (bfirst == blast) {                                    // fast path: the step lies in one bin (or none)
+                if (bfirst >= 0 && bfirst < nb) {
+#pragma unroll
+                    for (int q = 0; q < NV; ++q) {
+                        if (q >= nv) break;
+                        const double w = wave_sum(v[q]);
+                        if (lane == 0) row_acc[q * nb + bfirst] += w;
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int o = 1; o < 64; o <<= 1) {                   // segmented inclusive scan over runs of equal b
+                    const int bo = __shfl_up(b, o, 64);
+                    const bool same = lane >= o && bo == b;
+#pragma unroll
+                    for (int q = 0; q < NV; ++q) {
+                        const double w = __shfl_up(v[q], o, 64);
+                        if (same) v[q] += w;
+                    }
+                }
+                const int bn = __shfl_down(b, 1, 64);
+                if (ok && (lane == 63 || bn != b)) {
+#pragma unroll
+                    for (int q = 0; q < NV; ++q) if (q < nv) row_acc[q * nb + b] += v[q];
+                }
+            }
+        }
+    }
+    __syncthreads();
+    for (int q = tid; q < nv * nb; q += blockDim.x) {
+        double s = 0.0;
+        for (int w = 0; w < FB_SEP_WAVES; ++w) s += acc[(size_t)w * nv * nb + q];
+        partial[(size_t)q * gridDim.x + blockIdx.x] = s;              // [value][workgroup]: see k_bin_finish
+    }
+}
+
 }  // namespace fb

@@ -1,4 +1,5 @@
 // Host launchers of the element-wise kernels for one precision (FB_REAL / FB_SUFFIX).
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include "fb_plan.h"
@@ -320,6 +321,59 @@ int FBI(crop_full)(fb_plan* p, const void* f, void* h, hipStream_t s) {
     hipLaunchKernelGGL((k_crop_full<real_t>), mode_grid(p, p->NZV, bs), dim3(bs), 0, s, (const cplx_t*)f, (cplx_t*)h,
                        geom(p)); }
     FB_LAUNCH_CHECK("k_crop_full");
+    return FB_OK;
+}
+
+// ---- two-point correlation function (kernels: fb_field_kernels.h, k_cross_power / k_sep_bin) ------------------------
+int FBI(cross_power)(fb_plan* p, const void* a, const void* b, void* out, double scale, hipStream_t s) {
+    const long long n = (long long)p->N * p->NR * p->NZP;
+    const long long blocks = std::min((n + 255) / 256, 8LL * p->num_cu * 8);          // 8 resident 256-lane groups per CU, 8 rounds
+    { FbProfScope _ps(p, FBK_FILTER, s);
+    hipLaunchKernelGGL((k_cross_power<real_t>), dim3((unsigned)blocks), dim3(256), 0, s, (const cplx_t*)a, (const cplx_t*)b,
+                       (cplx_t*)out, geom(p), scale); }
+    FB_LAUNCH_CHECK("k_cross_power");
+    return FB_OK;
+}
+// out_dev[nv][nbins] (nv = nl, or 2 with geom: cells, sum |s|); edges_dev[nbins + 1] on the device, elast = its last value
+int FBI(sep_bin)(fb_plan* p, const void* real, const double* edges_dev, double elast, int nbins, int nl, int geom_only,
+                 double* out_dev, hipStream_t s) {
+    SepGeom sg;
+    sg.edges = edges_dev; sg.nbins = nbins; sg.nl = nl; sg.N = p->N;
+    for (int a = 0; a < 3; ++a) {
+        sg.h[a] = p->L[a] / (double)p->N;
+        // |s| >= |m_a| L_a / N: no cell with |m_a| > elast N / L_a reaches a bin (one more for rounding)
+        const double q = std::floor(elast * (double)p->N / p->L[a]) + 1.0;
+        sg.M[a] = q >= (double)(p->N / 2) ? p->N / 2 : (int)q;
+    }
+    const int nv = geom_only ? 2 : nl;
+    const size_t lds = (size_t)(nbins + 1) * 8 + (size_t)FB_SEP_WAVES * nv * nbins * 8;
+    const long long rows = (long long)(sg.M[0] + 1) * (sg.M[1] + 1);
+    long long blocks = (rows + FB_SEP_WAVES - 1) / FB_SEP_WAVES;
+    if (blocks > p->prow) blocks = p->prow;
+    if (blocks < 1) blocks = 1;
+    const size_t need = (size_t)blocks * nv * nbins;
+    if (need > p->sep_partials_cap) {
+        if (p->sep_partials) { FB_HIP(hipFree(p->sep_partials)); p->sep_partials = nullptr; p->sep_partials_cap = 0; }
+        FB_HIP(hipMalloc((void**)&p->sep_partials, need * sizeof(double)));
+        p->sep_partials_cap = need;
+    }
+    if (lds > 65536) {             // more than 2 x 256 bins x 3 multipoles: up to 106 KiB of the CU's 160 KiB (nbins <= 1024)
+        FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sep_bin<real_t, true>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sep_bin<real_t, false>),
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    }
+    { FbProfScope _ps(p, FBK_BIN, s);
+    if (geom_only)
+        hipLaunchKernelGGL((k_sep_bin<real_t, true>), dim3((unsigned)blocks), dim3(64 * FB_SEP_WAVES), lds, s, (const real_t*)real,
+                           p->sep_partials, sg);
+    else
+        hipLaunchKernelGGL((k_sep_bin<real_t, false>), dim3((unsigned)blocks), dim3(64 * FB_SEP_WAVES), lds, s, (const real_t*)real,
+                           p->sep_partials, sg); }
+    FB_LAUNCH_CHECK("k_sep_bin");
+    { FbProfScope _ps(p, FBK_BIN, s);
+    hipLaunchKernelGGL(k_bin_finish, dim3(nv * nbins), dim3(256), 0, s, p->sep_partials, (int)blocks, nv * nbins, out_dev); }
+    FB_LAUNCH_CHECK("k_bin_finish");
     return FB_OK;
 }
 

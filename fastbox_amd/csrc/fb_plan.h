@@ -75,6 +75,13 @@ struct fb_plan {
     long long exp_rows = 0;
     long long exp_base = 0;           // block offset of the plane batch being launched (fb_fft_launch.inc yz_passes)
 
+    // correlation function (fb_bin_separation): edges on the device, and the data-independent sums (cells, sum |s|) per
+    // bin set already computed -- [edges..., cells..., sum |s|...] per entry, most recent last
+    double* sep_edges = nullptr;      // [FB_MAX_SEP_BINS + 1]
+    std::vector<std::vector<double>> sep_geom;
+    double* sep_partials = nullptr;   // [nv nbins][workgroups] of k_sep_bin (grown on demand: up to 3 x 1024 values per workgroup)
+    size_t sep_partials_cap = 0;      // doubles
+
     // second stream for alternate plane batches of the y/z passes (created on first use)
     hipStream_t aux_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -112,6 +119,7 @@ struct FbProfScope {
 };
 
 #define FB_MAX_BINS 256
+#define FB_MAX_SEP_BINS 1024     // separation bins of fb_bin_separation: the default edges of a 2048^3 box (dr = L/N, rmax = L/2)
 #define FB_SCRATCH 8192
 
 void fb_set_error(const std::string& msg);
@@ -164,6 +172,9 @@ int fb_hip_check(hipError_t e, const char* what);
                               const double* ratio, void* out, hipStream_t s); \
     int fbi_sky_noise_cube_##sfx(fb_plan* p, const double* sigma, const void* unit, uint64_t seed, void* out, \
                                  hipStream_t s); \
+    int fbi_cross_power_##sfx(fb_plan* p, const void* a, const void* b, void* out, double scale, hipStream_t s); \
+    int fbi_sep_bin_##sfx(fb_plan* p, const void* real, const double* edges_dev, double elast, int nbins, int nl, \
+                          int geom_only, double* out_dev, hipStream_t s); \
     int fbi_bin_power_##sfx(fb_plan* p, const void* spec, int layout, int filter_kind, const double* prm, \
                             const void* table, double* sums_dev, hipStream_t s); \
     int fbi_apply_filter_##sfx(fb_plan* p, const void* in, void* out, int layout, int kind, const double* prm, \

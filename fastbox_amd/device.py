@@ -687,6 +687,21 @@ class Engine(object):
             self._cnt_cache = c
         return c
 
+    # -- correlation function -------------------------------------------------------------
+    def correlation(self, real1, real2, edges, lmax):
+        """fb_correlation_function: the record [npairs, sum |s|, sum xi L_l for l = 0, 2, .. lmax] per bin (host, fp64) of
+        the auto- (real2 None) or cross-correlation of two real device fields.  Work buffers come from the pool; waits for
+        the stream."""
+        edges = np.ascontiguousarray(edges, dtype=np.float64)
+        nb = edges.size - 1
+        out = np.zeros((2 + lmax // 2 + 1) * nb)
+        p1, p2 = real1.ptr, (real2.ptr if real2 is not None else None)
+        wh1, wr = self.empty(HALF), self.empty(REAL)
+        wh2 = self.empty(HALF) if real2 is not None else None
+        _lib.call("fb_correlation_function", self._plan, p1, p2, wh1.ptr, wh2.ptr if wh2 is not None else None, wr.ptr,
+                  edges.ctypes.data_as(_lib.P_double), nb, int(lmax), out.ctypes.data_as(_lib.P_double), self.stream)
+        return out
+
     # -- profiling ------------------------------------------------------------------------
     PROF_NAMES = ("fft_strided", "fft_contig", "colour", "bin", "filter", "velpot", "realop", "rsd", "layout",
                   "fft_gen", "fft_bin", "pca")

@@ -228,3 +228,52 @@ def bin_counts(N, Lside, bins):
     k = 2. * np.pi * np.sqrt(a[:, None, None] + a[None, :, None] + a[None, None, :])
     idx = np.digitize(k.ravel(), bins)
     return np.bincount(idx, minlength=bins.size + 1)[:bins.size].astype(np.float64)
+
+
+# ---- two-point correlation function (CosmoBox.correlation_function) ------------------------------------------------------
+POLES = (0, 2, 4)
+SEP_MAX_BINS = 1024          # FB_MAX_SEP_BINS of the library: dr = L/N up to rmax = L/2 at N = 2048
+
+
+def separation_edges(L, N, dr=None, rmin=0., rmax=None, rbins=None):
+    """Bin edges in separation: ``rbins`` as given, or np.arange(rmin, rmax + dr/2, dr) with dr = min(L_a)/N and
+    rmax = min(L_a)/2 by default (nbodykit's FFTCorr(dr=, rmin=, rmax=) grid).  Strictly ascending, first edge >= 0,
+    at least one bin and at most 1024 (the default edges of a 2048^3 box); ValueError otherwise."""
+    if rbins is not None:
+        edges = np.array(rbins, dtype=np.float64)
+    else:
+        lmin = float(np.min(L))
+        dr = lmin / N if dr is None else float(dr)
+        rmax = 0.5 * lmin if rmax is None else float(rmax)
+        if not dr > 0:
+            raise ValueError("dr must be positive")
+        edges = np.arange(float(rmin), rmax + 0.5 * dr, dr, dtype=np.float64)
+    if edges.ndim != 1 or edges.size < 2 or edges.size > SEP_MAX_BINS + 1:
+        raise ValueError("separation bins: between 2 and %d edges (1 to %d bins), got %r"
+                         % (SEP_MAX_BINS + 1, SEP_MAX_BINS, edges.shape))
+    if not np.all(np.isfinite(edges[:-1])) or not edges[0] >= 0. or not np.all(np.diff(edges) > 0):
+        raise ValueError("separation bin edges must be strictly ascending and start at >= 0")
+    return edges
+
+
+def check_poles(poles):
+    """The multipoles asked for as a tuple of ints out of (0, 2, 4); None -> (0,)."""
+    if poles is None:
+        return (0,)
+    ps = tuple(int(p) for p in np.atleast_1d(poles))
+    if not ps or any(p not in POLES for p in ps) or any(float(p) != q for p, q in zip(ps, np.atleast_1d(poles))):
+        raise ValueError("poles must be a subset of (0, 2, 4), got %r" % (poles,))
+    return ps
+
+
+def finish_correlation(raw, nbins, poles):
+    """(r, xi, npairs) from fb_bin_separation's record [npairs, sum |s|, sum xi L_l for l = 0, 2, .. lmax]:
+    r = mean |s| per bin (nbodykit's r column), xi_l = (2l + 1) sum xi L_l / npairs; empty bins NaN."""
+    raw = np.asarray(raw, dtype=np.float64)
+    npairs = raw[:nbins].copy()
+    with np.errstate(all="ignore"):
+        empty = npairs == 0
+        r = np.where(empty, np.nan, raw[nbins:2 * nbins] / npairs)
+        xi = np.array([np.where(empty, np.nan, (2 * l + 1) * raw[(2 + l // 2) * nbins:(3 + l // 2) * nbins] / npairs)
+                       for l in poles])
+    return r, xi, npairs

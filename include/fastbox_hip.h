@@ -183,6 +183,32 @@ int fb_montecarlo_power(fb_plan* plan, uint64_t seed, uint64_t first, uint64_t s
 /* number of full-grid modes per bin for the current bin set (host array, nbins doubles) */
 int fb_bin_counts(fb_plan* plan, double* count);
 
+/* ---- two-point correlation function ------------------------------------------------------------------------ */
+/* What the reference's examples end with, through nbodykit: examples/example_corr_fn.py:38-47
+ * (FFTCorr(first=mesh, mode='1d', los=[0,0,1], dr=2., rmin=10., rmax=200.) of delta_x and of lognormal(delta_x)), and step
+ * (6) of examples/End-to-end_simulation.ipynb / "Example end-to-end analysis.ipynb" (the same call on the true and on the
+ * PCA-cleaned cube, dr=2., rmin=20., rmax=200.).  Definition, for real fields d_1, d_2 (auto: d_2 = d_1):
+ *   D_a = fftn(d_a - mean(d_a)),  xi(s) = ifftn(conj(D_1) D_2) / N^3 = (1/N^3) sum_x d_1(x) d_2(x + s)  (periodic);
+ *   s_a = m_a (L_a / N), m_a the signed index (Nyquist negative); |s| = sqrt((s_x s_x + s_y s_y) + s_z s_z) in fp64,
+ *   no contraction; mu = s_z / |s| (0 at s = 0; the line of sight is z); bin b = [edges[b], edges[b+1]), i.e.
+ *   np.digitize(|s|, edges) - 1, separations outside [edges[0], edges[nbins]) dropped.
+ * Nothing is fused into an FFT pass: every grid a plan accepts.
+ * fb_cross_power_half: half_out = conj(half1) half2 * scale on half spectra (half2 = NULL: |half1|^2, imaginary part 0), the
+ *   k = 0 mode set to 0 (the mean removed).  half_out may be half1 or half2.  fb_fft_c2r applies exactly the scale it is given
+ *   (no implicit 1/N^3): scale = 1/N^6 here and 1 there deliver xi.
+ * fb_bin_separation: per-bin sums over the separations of a real field xi; edges[nbins + 1] strictly ascending, edges[0] >= 0,
+ *   1 <= nbins <= 1024, lmax 0, 2 or 4 (FB_ERR_INVALID otherwise).  out_host[(2 + lmax/2 + 1) nbins] = npairs[nbins] (cells per
+ *   bin), sum_r[nbins] (sum |s|), then sum[lmax/2 + 1][nbins] = sum xi(s) L_l(mu), l = 0, 2, ..  (xi_l = (2l + 1) sum / npairs;
+ *   nbodykit's r column = sum_r / npairs).  npairs and sum_r do not depend on the data: computed once per bin set and kept in the
+ *   plan.  Synchronises the stream.
+ * fb_correlation_function: the whole chain -- fb_fft_r2c of real1 (and real2, NULL: auto-correlation) into work_half1
+ *   (work_half2), fb_cross_power_half, fb_fft_c2r into work_real (which then holds xi), fb_bin_separation.  Synchronises. */
+int fb_cross_power_half(fb_plan* plan, const void* half1, const void* half2, void* half_out, double scale, void* stream);
+int fb_bin_separation(fb_plan* plan, const void* real, const double* edges, int nbins, int lmax, double* out_host,
+                      void* stream);
+int fb_correlation_function(fb_plan* plan, const void* real1, const void* real2, void* work_half1, void* work_half2,
+                            void* work_real, const double* edges, int nbins, int lmax, double* out_host, void* stream);
+
 /* ---- transfer functions (apply_transfer_fn box.py:374-379, smooth_field :651-653) ---------- */
 #define FB_FILT_TABLE 0          /* table: real multiplier, same layout as the field */
 #define FB_FILT_BEAM_HIGHPASS 1  /* (1-exp(-.5(|kpar|/p0)^p2)) [p0>0] * exp(-.5(kperp/p1)^2) [p1>0] */
