@@ -72,6 +72,14 @@ SIGNATURES = {
     "fb_bin_separation": (c_int, [c_void_p, c_void_p, P_double, c_int, c_int, P_double, c_void_p]),
     "fb_correlation_function": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, P_double, c_int, c_int,
                                         P_double, c_void_p]),
+    "fb_halo_lambda": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_int, c_double, c_double, c_int,
+                               c_void_p, c_void_p]),
+    "fb_halo_counts": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_int, c_double, c_double, c_int,
+                               c_u64, c_u64, c_void_p, P_i32, c_void_p]),
+    "fb_halo_catalogue_size": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_i64), c_void_p]),
+    "fb_halo_catalogue": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_int, c_u64, c_u64, c_void_p, c_void_p]),
+    "fb_paint": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_void_p]),
+    "fb_paint_compensate": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
     "fb_real_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_void_p]),
     "fb_real_multiply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fb_real_to_complex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),

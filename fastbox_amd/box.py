@@ -889,6 +889,22 @@ class CosmoBox(object):
         r, xi, npairs = hostgeom.finish_correlation(raw, edges.size - 1, ps)
         return r, (xi[0].copy() if poles is None else xi), npairs
 
+    # ------------------------------------------------------------ painting a catalogue
+    def paint_catalogue(self, positions, weights=None, window='cic', compensated=False):
+        """Additive: mass assignment of a catalogue onto this box's grid, what the reference's examples take from nbodykit as
+        ``ArrayCatalog({'Position': pos}).to_mesh(Nmesh=N, BoxSize=L, window=..., compensated=...)``
+        (examples/example_halos.py).  ``positions``: a HaloCatalogue or a host (n, 3) array (comoving, periodic);
+        ``weights``: optional length-n host array or float64 device tensor.  Returns a real DeviceArray holding
+        sum(weight * W), node m at m L_a / N, u = x N / L_a:
+
+            'ngp': node floor(u + 1/2);  'cic': floor(u), floor(u) + 1 with 1 - f, f;
+            'tsc': floor(u + 1/2) + (-1, 0, 1) with (1/2 - d)^2 / 2, 3/4 - d^2, (1/2 + d)^2 / 2.
+
+        ``compensated``: every Fourier mode divided by prod_a sinc(pi m_a / N)^p, p = 1, 2, 3.  The mesh is the same bit for
+        bit from call to call (fixed-point accumulation).  Agreement with nbodykit itself is intended but unverified."""
+        from . import halos
+        return halos.paint(self, positions, weights=weights, window=window, compensated=compensated)
+
     def sigmaR(self, R):
         """RMS of the field smoothed with a top-hat of R Mpc/h, from the binned power
         spectrum (box.py:657-683; scipy's simps is spelled simpson since 1.14)."""

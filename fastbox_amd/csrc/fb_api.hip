@@ -1,6 +1,7 @@
 // extern "C" surface of libfastbox_hip.so (see include/fastbox_hip.h).
 #include "../../include/fastbox_hip.h"
 #include "fb_plan.h"
+#include "fb_api_util.h"
 #include <dlfcn.h>
 #include <rccl/rccl.h>           // types and prototypes only: the functions are looked up in a dlopen'ed librccl (fb_comm.inc)
 #include <algorithm>
@@ -23,32 +24,6 @@ int fb_hip_check(hipError_t e, const char* what) {
     return e == hipErrorOutOfMemory ? FB_ERR_NOMEM : FB_ERR_HIP;
 }
 
-// (every entry point starts with an argument check: it also reads away a stale "last error" some other user of the
-// HIP runtime may have left in this thread, so that the launch checks below report this call's errors only)
-#define FB_REQUIRE(cond, msg) do { (void)hipGetLastError(); if (!(cond)) { fb_set_error(msg); return FB_ERR_INVALID; } } while (0)
-#define FB_DISPATCH(p, call32, call64) ((p)->prec == 4 ? (call32) : (call64))
-// A plan belongs to one device.  Every entry point that takes a plan makes that device current for the duration of the
-// call (allocations, NULL-stream launches and the plan's own auxiliary stream / events all follow the current device)
-// and puts the caller's device back when it returns -- other users of the HIP runtime in this thread (torch, RCCL)
-// keep the current device they had -- so plans on different GPUs can be used from one thread in any order.
-namespace {
-struct FbDeviceGuard {
-    int prev = -1;
-    bool changed = false;
-    int enter(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) { prev = -1; (void)hipGetLastError(); }
-        if (prev != dev) {
-            const int r = fb_hip_check(hipSetDevice(dev), "hipSetDevice");
-            if (r) return r;
-            changed = prev >= 0;
-        }
-        return FB_OK;
-    }
-    ~FbDeviceGuard() { if (changed) (void)hipSetDevice(prev); }
-};
-}  // namespace
-#define FB_USE_DEVICE(p) FbDeviceGuard _fb_devguard; do { const int _r = _fb_devguard.enter((p)->device); if (_r) return _r; } while (0)
-
 namespace {
 template <typename T> int upload(T** dst, const T* src, size_t n) {
     FB_HIP(hipMalloc(reinterpret_cast<void**>(dst), n * sizeof(T)));
@@ -70,7 +45,7 @@ template <typename T> int make_twiddles(void** out, int N) {
 
 extern "C" {
 
-int fb_version(void) { return 101; }
+int fb_version(void) { return 102; }
 const char* fb_last_error(void) { return g_last_error.c_str(); }
 
 int fb_device_count(int* count) {
@@ -153,7 +128,8 @@ int fb_plan_destroy(fb_plan* p) {
     (void)fb_comm_destroy(p);
     (void)hipSetDevice(p->device);
     void* ptrs[] = {p->tw, p->axis2, p->ksc, p->kpar, p->zgrid, p->amp_shell, p->amp_sym, p->kperp_tab, p->pca_work, p->bins, p->thr, p->counts,
-                    p->partials, p->scratch, p->bin_partials, p->exp_partials, p->plane_buf, p->sep_edges, p->sep_partials};
+                    p->partials, p->scratch, p->bin_partials, p->exp_partials, p->plane_buf, p->sep_edges, p->sep_partials,
+                    p->halo_small, p->halo_work, p->halo_acc};
     for (void* q : ptrs) if (q) (void)hipFree(q);
     if (p->aux_stream) { (void)hipStreamSynchronize(p->aux_stream); (void)hipStreamDestroy(p->aux_stream); }
     if (p->ev_fork) (void)hipEventDestroy(p->ev_fork);

@@ -82,6 +82,13 @@ struct fb_plan {
     double* sep_partials = nullptr;   // [nv nbins][workgroups] of k_sep_bin (grown on demand: up to 3 x 1024 values per workgroup)
     size_t sep_partials_cap = 0;      // doubles
 
+    // halo tracers (fb_halo.hip): reduction partials, the catalogue's (count, block) tables, the painting accumulators
+    void* halo_small = nullptr;       // [FB_HALO_SMALL] bytes
+    void* halo_work = nullptr;        // grown on demand
+    size_t halo_work_cap = 0;         // bytes
+    void* halo_acc = nullptr;         // grown on demand
+    size_t halo_acc_cap = 0;          // bytes
+
     // second stream for alternate plane batches of the y/z passes (created on first use)
     hipStream_t aux_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;

@@ -105,3 +105,75 @@ def stream_normals(n, stream, seed, realisation=0, dtype=np.float64):
 def los_noise(N, seed, dtype=np.float64):
     """Standard normals n(i,j,m) of the redshift-space small-scale velocities (stream 1)."""
     return stream_normals(N ** 3, 1, seed, 0, dtype).reshape(N, N, N)
+
+
+# ---- halo tracers (fb_halo.hip): Poisson counts on stream 5, catalogue scatter on stream 6 ----------------------------
+POISSON_TAIL = 1e-20
+
+
+def poisson_uniforms(n, seed, realisation=0, first=0):
+    """The uniform of voxels first .. first+n-1: (w + 1/2) 2^-53, w = (o0 << 21) | (o1 >> 11) of Philox call `voxel`, stream 5."""
+    o = _call(np.arange(first, first + n, dtype=np.uint64), 5, seed, realisation)
+    w = (o[0] << np.uint64(21)) | (o[1] >> np.uint64(11))
+    return (w.astype(np.float64) + 0.5) * 1.1102230246251565e-16
+
+
+def poisson_inverse(lam, u):
+    """Poisson variates by inversion of the CDF, step for step as the device (fb_halo.hip poisson_inverse): start at the
+    mode m = floor(lam) with pmf exp((m ln lam - lam) - lgamma(m + 1)), sum the mass below it downwards until a term is below
+    1e-20, then walk the CDF down or up from the mode.  lam <= 0 or NaN -> 0.  Returns int64."""
+    import math
+    lam = np.asarray(lam, dtype=np.float64)
+    u = np.broadcast_to(np.asarray(u, dtype=np.float64), lam.shape)
+    out = np.zeros(lam.shape, dtype=np.int64)
+    pos = lam > 0.0
+    l, uu = lam[pos], u[pos]
+    m = np.floor(l)
+    mu, inv = np.unique(m, return_inverse=True)
+    lg = np.array([math.lgamma(x + 1.0) for x in mu])[inv.reshape(-1)]
+    pm = np.exp((m * np.log(l) - l) - lg)
+    L = np.zeros_like(l)
+    p, j = pm.copy(), m.copy()
+    act = j > 0
+    while act.any():
+        p[act] = p[act] * j[act] / l[act]
+        j[act] -= 1.0
+        L[act] += p[act]
+        act &= (j > 0) & (p >= POISSON_TAIL)
+    k = m.copy()
+    down = uu < L
+    # walk down: c = F(k - 1) on entry
+    c, p = L.copy(), pm.copy()
+    act = down & (k > 0)
+    res = np.where(down, 0.0, m)
+    while act.any():
+        p[act] = p[act] * k[act] / l[act]
+        k[act] -= 1.0
+        hit = act & (uu >= c - p)
+        res[hit] = k[hit]
+        c[act & ~hit] -= p[act & ~hit]
+        act &= ~hit & (k > 0)
+    # walk up
+    k, p, c = m.copy(), pm.copy(), L + pm
+    act = ~down & (uu >= c)
+    while act.any():
+        p[act] = p[act] * l[act] / (k[act] + 1.0)
+        k[act] += 1.0
+        c[act] += p[act]
+        act &= (uu >= c) & (p != 0.0)
+    up = ~down
+    res[up] = k[up]
+    out[pos] = res.astype(np.int64)
+    return out
+
+
+def stream_poisson(lam, seed, realisation=0):
+    """Host model of fb_halo_counts' draw: the counts of a (flattened, C order) lam field."""
+    lam = np.asarray(lam, dtype=np.float64)
+    return poisson_inverse(lam, poisson_uniforms(lam.size, seed, realisation).reshape(lam.shape))
+
+
+def scatter_uniforms(nh, seed, realisation=0):
+    """(nh, 3) offsets of the device-scattered catalogue: (1 - 1e-8) (o_a 2^-32), words 0-2 of Philox call h, stream 6."""
+    o = _call(np.arange(nh, dtype=np.uint64), 6, seed, realisation)
+    return np.stack([(1. - 1e-8) * (o[a].astype(np.float64) * 2.3283064365386963e-10) for a in range(3)], axis=-1)

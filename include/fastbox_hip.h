@@ -209,6 +209,50 @@ int fb_bin_separation(fb_plan* plan, const void* real, const double* edges, int 
 int fb_correlation_function(fb_plan* plan, const void* real1, const void* real2, void* work_half1, void* work_half2,
                             void* work_real, const double* edges, int nbins, int lmax, double* out_host, void* stream);
 
+/* ---- halo tracers (fastbox/halos.py, examples/example_halos.py) --------------------------------------------------- */
+/* fb_halo_lambda: the expected count per voxel, lam_out (DEVICE double[N^3]), exactly halo_count_field's expression
+ * (halos.py:92-114) in fp64 whatever the plan's precision:
+ *   delta_h = bias * delta;  log-normal: delta_h = exp(delta_h - s) / mean(exp(delta_h - s)) - 1 (s = 0 on fp64 plans, the
+ *   field's maximum of bias * delta on fp32 plans; mean = sum / N^3);  lam = (voxel_vol * nbar) * (1 + delta_h), each
+ *   operation rounded once (no contraction);  lam < 0 -> 0 unless log-normal;  NaN -> 0.
+ * nbar, bias: kind FB_HALO_SCALAR (value `*_val`, pointer unused), FB_HALO_ZPROFILE (DEVICE double[N], indexed by z),
+ * FB_HALO_FIELD (DEVICE field of the plan's precision), FB_HALO_FIELD_F64 (DEVICE double[N^3]).  voxel_vol = Lx Ly Lz / N^3.
+ * fb_halo_counts: the same lam, then a Poisson draw per voxel into counts_out (real field of the plan's precision holding
+ *   integers): inversion of the CDF with one uniform per voxel, u = (w + 1/2) 2^-53 with w = (o0 << 21) | (o1 >> 11) the
+ *   words of Philox call `voxel` of stream 5 (fb_rng.h), in fp64.  *too_large = 1 if some lam > 2^24 (those voxels get 0).
+ *   Synchronises the stream.                                                                                              */
+#define FB_HALO_SCALAR 0
+#define FB_HALO_ZPROFILE 1
+#define FB_HALO_FIELD 2
+#define FB_HALO_FIELD_F64 3
+int fb_halo_lambda(fb_plan* plan, const void* delta, const void* nbar, int nbar_kind, double nbar_val, const void* bias,
+                   int bias_kind, double bias_val, double voxel_vol, int lognormal, double* lam_out, void* stream);
+int fb_halo_counts(fb_plan* plan, const void* delta, const void* nbar, int nbar_kind, double nbar_val, const void* bias,
+                   int bias_kind, double bias_val, double voxel_vol, int lognormal, uint64_t seed, uint64_t realisation,
+                   void* counts_out, int* too_large, void* stream);
+/* Halo catalogue (realise_halo_catalogue, halos.py:120-176) of a counts field (real field of the plan's precision, non-negative
+ * integers).  fb_halo_catalogue_size: kmax_total[0] = the largest count, [1] = the number of halos (FB_ERR_INVALID if a value
+ * is negative, not an integer or not finite); synchronises.  fb_halo_catalogue: pos_out (DEVICE double[total][3]) in the
+ * reference's order -- ascending count; within a count, voxels in C order, each repeated `count` times -- with
+ * pos[h][a] = (i_a + u) * (L_a / N), two fp64 operations.  scatter 0: u = 0; 1: u = uniforms[3 h + a] (DEVICE double[3 total]);
+ * 2: u = (1 - 1e-8) * (o_a 2^-32), o_a the words of Philox call h of stream 6.  Asynchronous (plan-owned work tables).          */
+int fb_halo_catalogue_size(fb_plan* plan, const void* counts, int64_t* kmax_total, void* stream);
+int fb_halo_catalogue(fb_plan* plan, const void* counts, int64_t kmax, int64_t total, const double* uniforms, int scatter,
+                      uint64_t seed, uint64_t realisation, double* pos_out, void* stream);
+/* Mass assignment (nbodykit's to_mesh, examples/example_halos.py): real_out = sum over particles of weight * W, periodic.
+ * pos: DEVICE double[n][3]; weights: DEVICE double[n] or NULL (all 1).  Node m sits at m L_a / N, u = x N / L_a:
+ *   NGP: node floor(u + 1/2);  CIC: floor(u), floor(u) + 1 with 1 - f, f (f = u - floor(u));
+ *   TSC: floor(u + 1/2) + (-1, 0, 1) with 1/2 (1/2 - d)^2, 3/4 - d^2, 1/2 (1/2 + d)^2 (d = u - floor(u + 1/2)).
+ * Accumulated in fixed point (int64; two words on fp64 plans): the result does not depend on the order of the adds and is
+ * the same bit for bit from call to call.  At most 2^31 contributions per node.  Asynchronous.
+ * fb_paint_compensate: real_inout = ifftn(fftn(real_inout) / prod_a sinc(pi m_a / N)^p), p = window + 1 (1 NGP, 2 CIC,
+ *   3 TSC), m_a the signed FFT index; work_half is scratch (half-spectrum sized).                                         */
+#define FB_WINDOW_NGP 0
+#define FB_WINDOW_CIC 1
+#define FB_WINDOW_TSC 2
+int fb_paint(fb_plan* plan, const double* pos, const double* weights, int64_t n, int window, void* real_out, void* stream);
+int fb_paint_compensate(fb_plan* plan, void* real_inout, void* work_half, int window, void* stream);
+
 /* ---- transfer functions (apply_transfer_fn box.py:374-379, smooth_field :651-653) ---------- */
 #define FB_FILT_TABLE 0          /* table: real multiplier, same layout as the field */
 #define FB_FILT_BEAM_HIGHPASS 1  /* (1-exp(-.5(|kpar|/p0)^p2)) [p0>0] * exp(-.5(kperp/p1)^2) [p1>0] */
