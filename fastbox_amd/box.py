@@ -871,6 +871,15 @@ class CosmoBox(object):
         L = (self.Lx, self.Ly, self.Lz)
         edges = hostgeom.separation_edges(L, N, dr=dr, rmin=rmin, rmax=rmax, rbins=rbins)
         ps = hostgeom.check_poles(poles)
+        d1, d2 = self._two_fields(delta_x, second)
+        raw = self.engine.correlation(d1, d2, edges, max(ps))
+        r, xi, npairs = hostgeom.finish_correlation(raw, edges.size - 1, ps)
+        return r, (xi[0].copy() if poles is None else xi), npairs
+
+    def _two_fields(self, delta_x, second):
+        """The real device fields of a two-point estimate: ``delta_x`` (default self.delta_x) and ``second`` (or None).
+        Shapes and owners are checked (ValueError) before anything is uploaded or evaluated."""
+        N = self.N
         for name, f in (("delta_x", delta_x), ("second", second)):
             if f is None:
                 continue
@@ -885,9 +894,47 @@ class CosmoBox(object):
                 raise ValueError("no delta_x: realise_density() first, or pass delta_x")
         d1 = self._as_real(delta_x)
         d2 = self._as_real(second) if second is not None else None
-        raw = self.engine.correlation(d1, d2, edges, max(ps))
-        r, xi, npairs = hostgeom.finish_correlation(raw, edges.size - 1, ps)
-        return r, (xi[0].copy() if poles is None else xi), npairs
+        return d1, d2
+
+    # ------------------------------------------------------------ power spectrum in (k, mu) bins
+    def power_spectrum(self, delta_x=None, second=None, mode='1d', dk=None, kmin=0., kmax=None, kbins=None, Nmu=5,
+                       poles=None):
+        """Additive: the power spectrum of a real field (or the cross spectrum with ``second``) in |k| or (|k|, mu) bins, with
+        multipoles -- what the reference's examples take from nbodykit as ``FFTPower(first=, second=, mode='1d' | '2d',
+        los=[0,0,1], Nmu=, dk=, kmin=, kmax=, poles=)`` (examples/example_box.py:48-52, examples/example_halos.py:46-52):
+
+            D_a = rfftn(d_a) (unnormalised),  P(k) = (Lx Ly Lz / N^6) Re(conj(D_1) D_2)   (fp64);
+            k_a = m_a (2 pi / L_a) (m_a the signed FFT index), mu = |k_z| / |k| (line of sight z);
+            every mode of the full grid but k = 0; k bin [e_b, e_b+1), mu bins np.linspace(0, 1, Nmu + 1) (mu = 1 in the last);
+            per cell: modes, k = mean |k|, mu = mean mu, power = mean P;
+            P_l(k_b) = (2l + 1) sum P(k) L_l(mu) / modes over the 1-d bin, l in (0, 2, 4).
+
+        ``mode='1d'``: returns ``(k, power, modes)`` of shape (nk,), or with ``poles`` (a subset of (0, 2, 4)) ``power`` of
+        shape (len(poles), nk).  ``mode='2d'``: returns ``(k, mu, power, modes)``, each (nk, Nmu); ``poles`` is refused.
+        Edges: ``kbins``, or np.arange(kmin, kmax + dk/2, dk) with dk = 2 pi / min(L), kmax = pi N / max(L) by default (N/2
+        bins on a cube); at most 1024 bins, 1 <= Nmu <= 128 and nk * Nmu <= 5120 (nk * 3 <= 5120 with poles 2 or 4).  Empty
+        cells are NaN in k, mu and power.  ``delta_x`` (default ``self.delta_x``) and ``second`` take whatever
+        ``correlation_function`` takes.  The box's state (delta_x, stored spectrum, realisation counter, P(k) bins) is left
+        as it was.  Bad arguments raise ValueError before any device work."""
+        if mode not in ('1d', '2d'):
+            raise ValueError("mode must be '1d' or '2d', got %r" % (mode,))
+        edges = hostgeom.power_edges((self.Lx, self.Ly, self.Lz), self.N, dk=dk, kmin=kmin, kmax=kmax, kbins=kbins)
+        hostgeom.mu_edges(Nmu)
+        nk = edges.size - 1
+        if mode == '2d':
+            if poles is not None:
+                raise ValueError("poles are a mode='1d' output")
+            nmu, ps = int(Nmu), None
+        else:
+            nmu, ps = 1, (None if poles is None else hostgeom.check_poles(poles))
+        lmax = 0 if ps is None else max(ps)
+        hostgeom.check_power_layout(nk, nmu, lmax)
+        d1, d2 = self._two_fields(delta_x, second)
+        raw = self.engine.power_kmu(d1, d2, edges, nmu, lmax)
+        k, mu, power, modes = hostgeom.finish_power(raw, nk, nmu, ps)
+        if mode == '2d':
+            return k, mu, power, modes
+        return k[:, 0].copy(), (power[:, 0].copy() if ps is None else power), modes[:, 0].copy()
 
     # ------------------------------------------------------------ painting a catalogue
     def paint_catalogue(self, positions, weights=None, window='cic', compensated=False):

@@ -82,6 +82,14 @@ struct fb_plan {
     double* sep_partials = nullptr;   // [nv nbins][workgroups] of k_sep_bin (grown on demand: up to 3 x 1024 values per workgroup)
     size_t sep_partials_cap = 0;      // doubles
 
+    // power spectrum in (k, mu) bins (fb_power.hip): the bin table on the device, per-workgroup partials, and the
+    // data-independent sums (modes, sum |k|, sum mu per cell) per (edges, nmu) already computed -- [edges..., nmu, modes...,
+    // sum |k|..., sum mu...] per entry, most recent last
+    double* pk_tab = nullptr;         // [FB_PK_MAX_K + FB_PK_MAX_MU + 2]
+    double* pk_partials = nullptr;    // [values][workgroups] of k_pk_bin (grown on demand)
+    size_t pk_partials_cap = 0;       // doubles
+    std::vector<std::vector<double>> pk_geom;
+
     // halo tracers (fb_halo.hip): reduction partials, the catalogue's (count, block) tables, the painting accumulators
     void* halo_small = nullptr;       // [FB_HALO_SMALL] bytes
     void* halo_work = nullptr;        // grown on demand
@@ -127,6 +135,9 @@ struct FbProfScope {
 
 #define FB_MAX_BINS 256
 #define FB_MAX_SEP_BINS 1024     // separation bins of fb_bin_separation: the default edges of a 2048^3 box (dr = L/N, rmax = L/2)
+#define FB_PK_MAX_K 1024         // k bins of fb_bin_power_kmu: the default edges of a 2048^3 box (dk = 2 pi / L up to Nyquist)
+#define FB_PK_MAX_MU 128         // mu bins
+#define FB_PK_MAX_VALUES 5120    // nk nmu (lmax / 2 + 1): one wave's LDS row of 40 KiB (1024 k bins x 5 mu bins)
 #define FB_SCRATCH 8192
 
 void fb_set_error(const std::string& msg);

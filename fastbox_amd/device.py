@@ -702,6 +702,21 @@ class Engine(object):
                   edges.ctypes.data_as(_lib.P_double), nb, int(lmax), out.ctypes.data_as(_lib.P_double), self.stream)
         return out
 
+    # -- power spectrum in (k, mu) bins ----------------------------------------------------
+    def power_kmu(self, real1, real2, kedges, nmu, lmax):
+        """fb_power_spectrum_kmu: the record [modes, sum |k|, sum mu, sum P per cell; sum P L_l per k bin for l = 2, .. lmax]
+        (host, fp64) of the auto- (real2 None) or cross-spectrum of two real device fields.  Work buffers come from the pool;
+        waits for the stream."""
+        kedges = np.ascontiguousarray(kedges, dtype=np.float64)
+        nk = kedges.size - 1
+        out = np.zeros(4 * nk * nmu + (lmax // 2) * nk)
+        wh1 = self.empty(HALF)
+        wh2 = self.empty(HALF) if real2 is not None else None
+        _lib.call("fb_power_spectrum_kmu", self._plan, real1.ptr, real2.ptr if real2 is not None else None, wh1.ptr,
+                  wh2.ptr if wh2 is not None else None, kedges.ctypes.data_as(_lib.P_double), nk, int(nmu), int(lmax),
+                  out.ctypes.data_as(_lib.P_double), self.stream)
+        return out
+
     # -- profiling ------------------------------------------------------------------------
     PROF_NAMES = ("fft_strided", "fft_contig", "colour", "bin", "filter", "velpot", "realop", "rsd", "layout",
                   "fft_gen", "fft_bin", "pca")

@@ -277,3 +277,66 @@ def finish_correlation(raw, nbins, poles):
         xi = np.array([np.where(empty, np.nan, (2 * l + 1) * raw[(2 + l // 2) * nbins:(3 + l // 2) * nbins] / npairs)
                        for l in poles])
     return r, xi, npairs
+
+
+# ---- power spectrum in (k, mu) bins (CosmoBox.power_spectrum) -------------------------------------------------------------
+PK_MAX_K = 1024              # FB_PK_MAX_K of the library: dk = 2 pi / L up to Nyquist at N = 2048
+PK_MAX_MU = 128              # FB_PK_MAX_MU
+PK_MAX_VALUES = 5120         # FB_PK_MAX_VALUES: nk * Nmu * (lmax / 2 + 1), one wave's 40 KiB LDS row (1024 x 5)
+
+
+def power_edges(L, N, dk=None, kmin=0., kmax=None, kbins=None):
+    """Bin edges in |k|: ``kbins`` as given, or np.arange(kmin, kmax + dk/2, dk) with dk = 2 pi / min(L_a) and
+    kmax = pi N / max(L_a) (the coarsest axis's Nyquist) by default -- nbodykit's FFTPower(dk=, kmin=, kmax=) grid, N/2 bins
+    on a cube.  Strictly ascending, first edge >= 0, all finite but the last, 1 to 1024 bins; ValueError otherwise."""
+    if kbins is not None:
+        edges = np.array(kbins, dtype=np.float64)
+    else:
+        dk = 2. * np.pi / float(np.min(L)) if dk is None else float(dk)
+        kmax = np.pi * N / float(np.max(L)) if kmax is None else float(kmax)
+        if not dk > 0:
+            raise ValueError("dk must be positive")
+        edges = np.arange(float(kmin), kmax + 0.5 * dk, dk, dtype=np.float64)
+    if edges.ndim != 1 or edges.size < 2 or edges.size > PK_MAX_K + 1:
+        raise ValueError("k bins: between 2 and %d edges (1 to %d bins), got %r" % (PK_MAX_K + 1, PK_MAX_K, edges.shape))
+    if not np.all(np.isfinite(edges[:-1])) or not edges[0] >= 0. or not np.all(np.diff(edges) > 0):
+        raise ValueError("k bin edges must be strictly ascending and start at >= 0")
+    return edges
+
+
+def mu_edges(Nmu):
+    """np.linspace(0, 1, Nmu + 1): nbodykit's mu bins (mu = 1 counted in the last); 1 <= Nmu <= 128, ValueError otherwise."""
+    if isinstance(Nmu, bool) or not isinstance(Nmu, (int, np.integer)) or not 1 <= Nmu <= PK_MAX_MU:
+        raise ValueError("Nmu must be an integer in 1..%d, got %r" % (PK_MAX_MU, Nmu))
+    return np.linspace(0., 1., int(Nmu) + 1)
+
+
+def check_power_layout(nk, nmu, lmax):
+    """ValueError unless nk * nmu * (lmax / 2 + 1) fits one wave's LDS row of the binning kernel."""
+    if nk * nmu * (lmax // 2 + 1) > PK_MAX_VALUES:
+        raise ValueError("%d k bins x %d mu bins x %d multipoles: at most %d cells x multipoles"
+                         % (nk, nmu, lmax // 2 + 1, PK_MAX_VALUES))
+
+
+def finish_power(raw, nk, nmu, poles=None):
+    """From fb_bin_power_kmu's record [modes, sum |k|, sum mu, sum P (nk * nmu each); sum P L_l (nk each), l = 2, .. lmax]:
+    (k, mu, power, modes), each (nk, nmu), with k, mu, power the means per cell (NaN where modes is 0); with ``poles``,
+    power is instead (len(poles), nk) of P_l = (2l + 1) sum P L_l / modes over each k bin (nmu must then be 1)."""
+    raw = np.asarray(raw, dtype=np.float64)
+    nc = nk * nmu
+    modes, sk, smu, sp = (raw[q * nc:(q + 1) * nc].reshape(nk, nmu).copy() for q in range(4))
+    with np.errstate(all="ignore"):
+        empty = modes == 0
+        k = np.where(empty, np.nan, sk / modes)
+        mu = np.where(empty, np.nan, smu / modes)
+        if poles is None:
+            return k, mu, np.where(empty, np.nan, sp / modes), modes
+        assert nmu == 1
+        m1, e1 = modes[:, 0], empty[:, 0]
+        sums = {0: sp[:, 0]}
+        for q, l in enumerate((2, 4)):
+            lo = 4 * nc + q * nk
+            if raw.size >= lo + nk:
+                sums[l] = raw[lo:lo + nk]
+        power = np.array([np.where(e1, np.nan, (2 * l + 1) * sums[l] / m1) for l in poles])
+    return k, mu, power, modes

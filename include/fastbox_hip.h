@@ -209,6 +209,33 @@ int fb_bin_separation(fb_plan* plan, const void* real, const double* edges, int 
 int fb_correlation_function(fb_plan* plan, const void* real1, const void* real2, void* work_half1, void* work_half2,
                             void* work_real, const double* edges, int nbins, int lmax, double* out_host, void* stream);
 
+/* ---- power spectrum in (k, mu) bins, cross spectra, multipoles ----------------------------------------------- */
+/* What the reference's examples take from nbodykit as FFTPower(first=, second=, mode='1d' | '2d', los=[0,0,1], Nmu=, dk=,
+ * kmin=, kmax=, poles=) (examples/example_box.py:48-52, examples/example_halos.py:46-52).  Definition, for real fields d_1,
+ * d_2 (auto: d_2 = d_1):
+ *   D_a = rfftn(d_a) (unnormalised); P(k) = (Lx Ly Lz / N^6) Re(conj(D_1(k)) D_2(k)), products and sums in fp64;
+ *   k_a = m_a (2 pi / L_a), m_a the signed index (Nyquist negative); |k| = sqrt((k_x k_x + k_y k_y) + k_z k_z) in fp64, no
+ *   contraction; mu = |k_z| / |k| (line of sight z).  Modes of the full grid: a half-spectrum cell with 0 < m_z < N/2 counts
+ *   twice, the planes m_z = 0 and N/2 once; k = 0 is excluded.  k bin b = [kedges[b], kedges[b+1]) = np.digitize(|k|,
+ *   kedges) - 1, modes outside [kedges[0], kedges[nk]) dropped; mu bin c = np.digitize(mu, np.linspace(0, 1, nmu + 1)) - 1
+ *   with mu >= 1 in the last bin.  Cell (b, c) has index b nmu + c.
+ * Limits (FB_ERR_INVALID otherwise): kedges[nk + 1] strictly ascending, kedges[0] >= 0, all finite but the last (which may be
+ *   inf); 1 <= nk <= 1024; 1 <= nmu <= 128; lmax 0, 2 or 4; nk nmu (lmax/2 + 1) <= 5120 (one wave's LDS row: 1024 k bins x 5 mu
+ *   bins, or 1024 x 1 with lmax 4).
+ * fb_bin_power_kmu: bins Re(conj(half1) half2) (half2 = NULL: |half1|^2) straight from the stored half spectra, without
+ *   writing the product.  out_host[4 nk nmu + (lmax/2) nk] (nc = nk nmu):
+ *     modes[nc] (full-grid modes per cell), sum_k[nc] (sum |k|), sum_mu[nc] (sum mu), sum_p[nc] (sum P),
+ *     then sum P L_l over each k bin's mu cells [nk] for l = 2, 4 up to lmax.
+ *   nbodykit's columns are k = sum_k / modes, mu = sum_mu / modes, power = sum_p / modes, and the multipoles
+ *   P_l = (2l + 1) sum P L_l / modes of the 1-d bin.  modes, sum_k and sum_mu do not depend on the data: computed once per
+ *   (kedges, nmu) and kept in the plan.  Synchronises the stream.
+ * fb_power_spectrum_kmu: fb_fft_r2c of real1 (and real2; NULL: auto spectrum) into work_half1 (work_half2), then
+ *   fb_bin_power_kmu.  Every grid a plan accepts.  Synchronises. */
+int fb_bin_power_kmu(fb_plan* plan, const void* half1, const void* half2, const double* kedges, int nk, int nmu, int lmax,
+                     double* out_host, void* stream);
+int fb_power_spectrum_kmu(fb_plan* plan, const void* real1, const void* real2, void* work_half1, void* work_half2,
+                          const double* kedges, int nk, int nmu, int lmax, double* out_host, void* stream);
+
 /* ---- halo tracers (fastbox/halos.py, examples/example_halos.py) --------------------------------------------------- */
 /* fb_halo_lambda: the expected count per voxel, lam_out (DEVICE double[N^3]), exactly halo_count_field's expression
  * (halos.py:92-114) in fp64 whatever the plan's precision:
