@@ -14,6 +14,6 @@ from .sky import ForegroundModel, NoiseModel      # noqa: F401
 from . import filters                             # noqa: F401
 from . import montecarlo                          # noqa: F401
 from .beams import BeamModel                      # noqa: F401
-from .halos import HaloDistribution, HaloCatalogue   # noqa: F401
+from .halos import HaloDistribution, HaloCatalogue, ColaParticles   # noqa: F401
 
 __version__ = "0.1.0"

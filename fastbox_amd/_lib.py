@@ -83,6 +83,15 @@ SIGNATURES = {
     "fb_halo_catalogue": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_int, c_u64, c_u64, c_void_p, c_void_p]),
     "fb_paint": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_void_p, c_void_p]),
     "fb_paint_compensate": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "fb_cola_lpt": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fb_cola_init": (c_int, [c_void_p, c_void_p, c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p]),
+    "fb_cola_force": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p]),
+    "fb_cola_kick": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, P_double, c_int, c_void_p]),
+    "fb_cola_velocity": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_double, c_double, c_double, c_void_p, c_int,
+                                 c_void_p]),
+    "fb_cola_grid_velocity": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fb_cola_run": (c_int, [c_void_p, c_void_p, c_int, P_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                            c_void_p, c_void_p, c_void_p, c_void_p]),
     "fb_real_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_void_p]),
     "fb_real_multiply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fb_real_to_complex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),

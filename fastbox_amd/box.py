@@ -704,6 +704,78 @@ class CosmoBox(object):
                 return lazy
         return self.engine.redshift_space(d, v, Hz, sigma_nl, noise, seed, method)
 
+    # ------------------------------------------------------------------- COLA
+    COLA_MAX_N = 1024
+
+    def realise_density_cola(self, redshift=None, redshift_init=15., keep_velocities=True, seed=None, inplace=True,
+                             n_steps=None, delta_lin=None, return_particles=False):
+        """Density (and velocities) of a COLA particle-mesh run on the device (box.py:463-589, which calls pycola3): N^3
+        particles on the box's grid, 2LPT initial positions at redshift_init, ``n_steps`` kick-drift-kick steps uniform in a
+        (None: ``int(1 + redshift_init)``, as the reference; 0: pure 2LPT at ``redshift``), CIC painting.  Definition and
+        deviations in DESIGN.md section 4.
+
+        Initial conditions: ``delta_lin`` (host array or real DeviceArray, the z = 0 linear density) or the box's own linear
+        field -- what ``realise_density(linear=True, redshift=0., inplace=False)`` would give now.  ``seed`` int: rng='numpy'
+        draws re, then im from ``np.random.RandomState(seed)``; rng='device' uses Philox (seed, realisation 0); neither
+        touches the global stream or the box's realisation counter.
+
+        Returns delta_x, or (delta_x, vel_x, vel_y, vel_z) with ``keep_velocities`` -- real DeviceArrays; velocities are
+        a dx/dt in km/s, painted with CIC and divided by the painted count (0 in empty cells).  ``return_particles`` appends a
+        ``ColaParticles`` (fp64 positions in Mpc and velocities in km/s on the device)."""
+        from . import cola
+        from .halos import ColaParticles
+        assert self.Lx == self.Ly == self.Lz, \
+            "realise_density_cola() requires a cubic box with Lx=Ly=Lz"
+        if redshift is None:
+            redshift = self.redshift
+        assert redshift_init > redshift, "Must have redshift_init > redshift"
+        n_steps = int(1 + redshift_init) if n_steps is None else int(n_steps)
+        if n_steps < 0:
+            raise ValueError("n_steps must be >= 0")
+        if self.N > self.COLA_MAX_N:
+            raise ValueError("realise_density_cola: a %d^3 run needs about %.0f GB of device memory; grids up to %d^3 are "
+                             "supported" % (self.N, cola.device_bytes(self.N, self.engine.precision, keep_velocities,
+                                                                      return_particles) / 1e9, self.COLA_MAX_N))
+        eng, N = self.engine, self.N
+        d0 = self._as_real(delta_lin) if delta_lin is not None else self._cola_linear_field(seed)
+        growth = cola.Growth(self.cosmo, _ccl)
+        st = eng.cola_run(d0, n_steps, cola.launch_table(growth, redshift, redshift_init, n_steps))
+        del d0
+        delta_x = st["delta"]
+        out = [delta_x]
+        if keep_velocities or return_particles:
+            P1, P2, fac = cola.velocity_coefficients(growth, redshift, self.cosmo['h'])
+            pvel = eng._alloc_bytes(24 * N ** 3) if return_particles else None
+            if keep_velocities:
+                vbuf = eng._alloc_bytes(8 * N ** 3)
+                for c in range(3):
+                    eng.cola_velocity(st, c, P1, P2, fac, vbuf.ptr)
+                    out.append(eng.cola_grid_velocity(st, vbuf.ptr))
+                del vbuf
+            if return_particles:
+                for c in range(3):
+                    eng.cola_velocity(st, c, P1, P2, fac, pvel.ptr + 8 * c, 3)
+                out.append(ColaParticles(eng, st["pos"], N ** 3, pvel))
+        del st
+        eng.sync()
+        if inplace:
+            self.delta_x = delta_x
+            self._delta_k = None
+        return out[0] if len(out) == 1 else tuple(out)
+
+    def _cola_linear_field(self, seed):
+        """The z = 0 linear density of realise_density_cola (see there)."""
+        if seed is None:
+            return self.realise_density(linear=True, redshift=0., inplace=False)
+        eng, N = self.engine, self.N
+        self._set_amplitude(1.0, True)
+        if self.rng == "numpy":
+            rs = np.random.RandomState(int(seed))
+            re = eng.upload(rs.normal(0.0, 1.0, (N, N, N)), REAL)
+            im = eng.upload(rs.normal(0.0, 1.0, (N, N, N)), REAL)
+            return eng.fft_c2r(eng.colour_noise(re, im), destroy=True)
+        return eng.fft_c2r(eng.colour_device(int(seed), 0), destroy=True)
+
     # ------------------------------------------------------------------- log-normal
     def lognormal(self, delta_x):
         """exp(delta)/<exp(delta)> - 1 (box.py:441-460).  Returned lazily: the field is

@@ -717,6 +717,41 @@ class Engine(object):
                   out.ctypes.data_as(_lib.P_double), self.stream)
         return out
 
+    # -- COLA particle mesh -------------------------------------------------------------------
+    def cola_buffers(self):
+        """The state of one COLA run: pos (fp64 [N^3][3]), psi1, psi2, pres, force ([3][N^3] plan precision) as raw
+        buffers; count, delta (real DeviceArrays); h1, h2 (work half spectra)."""
+        n3, rb = self.N ** 3, self.nbytes[REAL]
+        st = dict(pos=self._alloc_bytes(24 * n3))
+        for name in ("psi1", "psi2", "pres", "force"):
+            st[name] = self._alloc_bytes(3 * rb)
+        st.update(count=self.empty(REAL), delta=self.empty(REAL), h1=self.empty(HALF), h2=self.empty(HALF))
+        return st
+
+    def cola_run(self, delta0, n_steps, table):
+        """fb_cola_run from the real field delta0 with the coefficient table of fastbox_amd.cola.launch_table.  Returns the
+        state of cola_buffers() without the work buffers."""
+        st = self.cola_buffers()
+        tab = np.ascontiguousarray(table, dtype=np.float64)
+        _lib.call("fb_cola_run", self._plan, delta0.ptr, int(n_steps), tab.ctypes.data_as(_lib.P_double), st["pos"].ptr,
+                  st["psi1"].ptr, st["psi2"].ptr, st["pres"].ptr, st["force"].ptr, st["count"].ptr, st["delta"].ptr,
+                  st["h1"].ptr, st["h2"].ptr, self.stream)
+        for name in ("force", "h1", "h2"):
+            del st[name]
+        return st
+
+    def cola_velocity(self, st, comp, P1, P2, fac, out_ptr, stride=1):
+        """fb_cola_velocity: component `comp` of every particle's velocity into fp64 device memory at out_ptr."""
+        _lib.call("fb_cola_velocity", self._plan, st["psi1"].ptr, st["psi2"].ptr, st["pres"].ptr, int(comp), float(P1),
+                  float(P2), float(fac), out_ptr, int(stride), self.stream)
+
+    def cola_grid_velocity(self, st, vel_ptr):
+        """paint(w = v) / paint(w = 1) with CIC, 0 where nothing was painted: a real DeviceArray."""
+        out = self.empty(REAL)
+        _lib.call("fb_paint", self._plan, st["pos"].ptr, vel_ptr, self.N ** 3, 1, out.ptr, self.stream)
+        _lib.call("fb_cola_grid_velocity", self._plan, out.ptr, st["count"].ptr, self.stream)
+        return out
+
     # -- profiling ------------------------------------------------------------------------
     PROF_NAMES = ("fft_strided", "fft_contig", "colour", "bin", "filter", "velpot", "realop", "rsd", "layout",
                   "fft_gen", "fft_bin", "pca")

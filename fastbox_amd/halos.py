@@ -62,6 +62,19 @@ class HaloCatalogue(object):
         return "HaloCatalogue(%d halos)" % self.n
 
 
+class ColaParticles(HaloCatalogue):
+    """The particles of CosmoBox.realise_density_cola: positions (Mpc, wrapped to [0, L)) as a HaloCatalogue -- so
+    ``paint_catalogue`` takes them -- and ``velocities``, the peculiar velocities a dx/dt in km/s, fp64 (n, 3) on the device
+    (``np.asarray(p.velocities)`` is the host copy)."""
+
+    def __init__(self, engine, buf, n, vel_buf):
+        HaloCatalogue.__init__(self, engine, buf, n)
+        self.velocities = HaloCatalogue(engine, vel_buf, n)
+
+    def __repr__(self):
+        return "ColaParticles(%d particles)" % self.n
+
+
 def _next_realisation(box):
     r = getattr(box, "_halo_draws", 0)
     box._halo_draws = r + 1

@@ -280,6 +280,44 @@ int fb_halo_catalogue(fb_plan* plan, const void* counts, int64_t kmax, int64_t t
 int fb_paint(fb_plan* plan, const double* pos, const double* weights, int64_t n, int window, void* real_out, void* stream);
 int fb_paint_compensate(fb_plan* plan, void* real_inout, void* work_half, int window, void* stream);
 
+/* ---- COLA particle mesh (realise_density_cola, box.py:463-589; definition in DESIGN.md section 4) ---------------------------
+ * Cubic, single-GPU plans, N^3 particles.  Particle i starts on node i (C order) at q = m L / N, so "per-particle" arrays are
+ * real fields of the plan's precision: psi1, psi2, pres, force are [3][N^3] blocks (component-major, indexed by particle);
+ * positions are DEVICE double[N^3][3] in Mpc, wrapped to [0, L).  k_a = 2 pi m_a / L with m_a the signed FFT index
+ * (fftfreq: N/2 -> -N/2).  Every transform is fb_fft_r2c / fb_fft_c2r with scale 1/N^3; work_half1/2 are half-spectrum sized.
+ * Asynchronous.
+ * fb_cola_lpt: from delta0 (real, z = 0 linear density): psi1 = c2r(i k delta0(k) / k^2); the six phi_ab = c2r(k_a k_b
+ *   delta0(k) / k^2); S = phi_xx phi_yy + phi_xx phi_zz + phi_yy phi_zz - phi_xy^2 - phi_xz^2 - phi_yz^2 (one pass);
+ *   psi2 = c2r(-i k S(k) / k^2).  k = 0 is zeroed; i k_a and k_a k_b (a != b) are zeroed on the planes m_a = -N/2 (and
+ *   m_b = -N/2); k_a^2 is not.  work3: [3][N^3] real scratch.                                                               */
+int fb_cola_lpt(fb_plan* plan, const void* delta0, void* psi1, void* psi2, void* work3, void* work_half1, void* work_half2,
+                void* stream);
+/* fb_cola_init: pos = wrap(q + d1 psi1 + d2 psi2); pres = 0 (pres may be NULL).                                               */
+int fb_cola_init(fb_plan* plan, const void* psi1, const void* psi2, double d1, double d2, double* pos, void* pres, void* stream);
+/* fb_cola_force: count = fb_paint(pos, weights 1, CIC); delta = count - 1; force (NULL: stop there) = c2r(coef i k delta(k) /
+ *   k^2) per component, coef = (3/2) Omega_m.  No window deconvolution.                                                     */
+int fb_cola_force(fb_plan* plan, const double* pos, void* count, void* delta, void* force, double coef, void* work_half1,
+                  void* work_half2, void* stream);
+/* fb_cola_kick: per particle, F = the CIC readout of force at pos (fb_paint's nodes and weights); per component
+ *   pres += (F cK - dP1 psi1) - dP2 psi2, then (drift != 0) pos = wrap(pos + (pres Dr + dD1 psi1) + dD2 psi2).
+ *   coef: HOST double[6] = {cK, dP1, dP2, Dr, dD1, dD2}.                                                                      */
+int fb_cola_kick(fb_plan* plan, const void* force, const void* psi1, const void* psi2, void* pres, double* pos, const double* coef,
+                 int drift, void* stream);
+/* fb_cola_velocity: out[i stride] = fac ((pres + P1 psi1) + P2 psi2) of one component (0, 1, 2), DEVICE double; with
+ *   fac = 100 h / a this is the peculiar velocity a dx/dt in km/s.
+ * fb_cola_grid_velocity: num_inout = num_inout / count where count != 0, else 0 -- with num_inout = fb_paint(pos, v, CIC)
+ *   and count = fb_paint(pos, NULL, CIC) the mass-weighted CIC velocity on the mesh.                                          */
+int fb_cola_velocity(fb_plan* plan, const void* psi1, const void* psi2, const void* pres, int component, double P1, double P2,
+                     double fac, double* out, int stride, void* stream);
+int fb_cola_grid_velocity(fb_plan* plan, void* num_inout, const void* count, void* stream);
+/* fb_cola_run: the whole run.  coef: HOST double[3 + 6 (n_steps + 1)] (fastbox_amd/cola.py launch_table) =
+ *   {d1, d2, (3/2) Omega_m, then one fb_cola_kick row per launch}.  fb_cola_lpt (force as work3); fb_cola_init(d1, d2);
+ *   n_steps == 0: fb_cola_force without the force (count and delta only); else n_steps + 1 times fb_cola_force then
+ *   fb_cola_kick with row j, drifting in all launches but the last.  Leaves count, delta at the final positions, and pos, pres,
+ *   psi1, psi2 for fb_cola_velocity.                                                                                         */
+int fb_cola_run(fb_plan* plan, const void* delta0, int n_steps, const double* coef, double* pos, void* psi1, void* psi2, void* pres,
+                void* force, void* count, void* delta, void* work_half1, void* work_half2, void* stream);
+
 /* ---- transfer functions (apply_transfer_fn box.py:374-379, smooth_field :651-653) ---------- */
 #define FB_FILT_TABLE 0          /* table: real multiplier, same layout as the field */
 #define FB_FILT_BEAM_HIGHPASS 1  /* (1-exp(-.5(|kpar|/p0)^p2)) [p0>0] * exp(-.5(kperp/p1)^2) [p1>0] */
