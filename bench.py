@@ -22,12 +22,14 @@ what the last one returned (spectrum and delta_x, see dump_outputs) for output-f
 is already running under a launcher (WORLD_SIZE set).  Every rank runs independent realisations of the
 same box (Monte-Carlo replicas, no data-path collective; "scaling": "weak"); `value` is the whole-job rate.
 
-Prints ONE JSON line (see README / DESIGN.md for the fields).  Besides the contract's fields:
+Prints ONE JSON line (see README / DESIGN.md for the fields).  A plain run does only what the headline needs: it sets
+up, spins up, warms up, times the K steps, writes --dump-outputs and prints the line.  Besides the contract's fields:
   roofline           dominant kernel class (strided y FFT pass), HIP events on the launch stream.  With one stream
                      the brackets sit inside the timed region (every 7th launch); with several streams kernels of
                      different boxes share the chip, so the kernel is timed in a separate single-stream pass right
-                     after the timed region ("timed_in" says which)
+                     before the warm-up steps ("timed_in" says which), with --full only (null otherwise)
   pipeline_roofline  whole step against 8 TB/s, on SURVEY 8(d)'s model bytes and on the bytes actually moved
+With --full, also (each a measurement of its own; --no-extras / --no-cpu-baseline leave them out again):
   f64                the same step on a precision='f64' plan (the reference computes in complex128)
   config3            BASELINE configs[2]: gen -> v_z -> redshift space -> wedge filter -> P(k) + filtered field, independent
                      chains on --streams boxes as the headline's realisations (+ one_box, + the remap kernel's own roofline)
@@ -62,11 +64,15 @@ def parse(argv=None):
     ap.add_argument("--nsamp", type=int, default=512)
     ap.add_argument("--precision", default="f32", choices=["f32", "f64"])
     ap.add_argument("--nbins", type=int, default=20)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, every measurement of its own: the f64 / config3 / spectra-only / sizes "
+                         "legs, the un-overlapped roofline pass (several streams), strong scaling (N > 1) and the CPU "
+                         "baseline (N = 1).  Off: the line holds the headline and what the timed steps give")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: without the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="only the timed region and its roofline (no f64 / config3 / sizes / strong-scaling legs)")
+                    help="--full: only the timed region and its roofline (no f64 / config3 / sizes / strong-scaling legs)")
     ap.add_argument("--cpu-nsamp", type=int, default=0,
-                    help="grid of the CPU baseline sample; 0 = the benchmarked size itself up to 512^3 (one step, "
+                    help="--full: grid of the CPU baseline sample; 0 = the benchmarked size itself up to 512^3 (one step, "
                          "~23 s of one host core), 256^3 scaled by voxel count above that")
     ap.add_argument("--mode", default="replicas", choices=["replicas", "slab"],
                     help="replicas: every rank realises its own boxes (Monte-Carlo throughput, weak scaling; default). "
@@ -81,8 +87,8 @@ def parse(argv=None):
     ap.add_argument("--streams", type=int, default=2,
                     help="independent realisations are issued round-robin on this many HIP streams (boxes)")
     ap.add_argument("--sizes", default="128,256,1024,2048",
-                    help="N = 1: other grid sizes of the `sizes` leg (128^3 = BASELINE configs[0], the reference's own CPU-runnable case)")
-    ap.add_argument("--slab-sizes", default="1024,2048", help="N > 1: grid sizes of the `strong_scaling` leg")
+                    help="--full, N = 1: other grid sizes of the `sizes` leg (128^3 = BASELINE configs[0], the reference's own CPU-runnable case)")
+    ap.add_argument("--slab-sizes", default="1024,2048", help="--full, N > 1: grid sizes of the `strong_scaling` leg")
     ap.add_argument("--spin-up", type=float, default=0.15,
                     help="seconds of untimed steps of the same workload run directly before the warm-up steps: the GPU "
                          "raises its clocks over ~50 ms of load (tools/step_timeline.py: the first 20 steps after an idle "
@@ -97,7 +103,7 @@ def parse(argv=None):
                          "GPU when --streams 1, N/8 when several boxes share the GPU)")
     ap.add_argument("--plane-streams", type=int, default=None, help="1 | 2 streams for alternate plane batches")
     ap.add_argument("--no-one-box-pass", action="store_true",
-                    help="skip roofline.one_box_launch (profiler runs: keeps every launch of the roofline kernel the same size)")
+                    help="--full: skip roofline.one_box_launch (profiler runs: keeps every launch of the roofline kernel the same size)")
     ap.add_argument("--gaussian-only", action="store_true",
                     help="tuning aid: P(k) of the Gaussian field itself (no exp in the fused z pass); the line is then NOT "
                          "BASELINE's configs[1]")
@@ -534,11 +540,11 @@ def main():
             dist.barrier()
             torch.cuda.synchronize()
 
-    # The auxiliary legs run FIRST (rank 0): they are measurements of their own, and they leave the GPU at its
-    # sustained clocks, so that the timed region below is the steady state SURVEY 8(d) defines the metric on
+    # --full: the auxiliary legs run FIRST (rank 0), as measurements of their own.  With or without them, the spin-up
+    # below runs directly before the timed region, so that it is the steady state SURVEY 8(d) defines the metric on
     # (a cold start reads ~4 % low over a 20-step region: tools/step_timeline.py, profiles/r02_step_timeline.txt).
     extras = {}
-    if rank == 0 and not args.no_extras:
+    if rank == 0 and args.full and not args.no_extras:
         def guarded(name, fn):
             try:
                 extras[name] = fn()
@@ -570,7 +576,8 @@ def main():
     in_region = nstreams == 1             # event brackets inside the timed region only when kernels run alone
     ev_stride = 1 if args.all_kernel_events else max(1, args.kernel_event_stride)
     prof_steps = args.steps
-    if not in_region:
+    prof, prof_other, big = None, {}, None
+    if not in_region and args.full:
         # kernels of different boxes overlap in the timed region, so the roofline kernel is timed on its own here, on
         # ONE stream, directly before the warm-up steps (this pass also leaves the GPU at its sustained clocks)
         prof_steps = 40
@@ -591,7 +598,6 @@ def main():
         prof_other = eng.profile_stop()
         # the same kernel in the launches one box per GPU would use (plane batches sized to the whole Infinity Cache:
         # a launch carries a fixed fill and drain, so the larger launch reads closer to the kernel's own rate)
-        big = None
         try:
             if args.no_one_box_pass:
                 raise StopIteration
@@ -608,6 +614,9 @@ def main():
         finally:
             eng.set_plane_batching(*boxes[0]._bench_plane_batching)
             one().result()
+    # the first step on each box loads the step's kernels, which takes longer than the whole spin-up when nothing ran
+    # before it (no --full legs): it runs before the spin-up's clock starts, so that the spin-up is spent at full rate
+    _warm(step, len(boxes))
     import gc
     gc.collect()                          # BEFORE the spin-up: an idle gap directly before the timed region would let the
     gc.disable()                          # clocks drop again; a collector pause inside a 20 ms region would be 5 % of it
@@ -658,17 +667,6 @@ def main():
 
     # ---------------------------------------------------------------- rank 0: the line
     s = 4 if args.precision == "f32" else 8
-    timed_in = "timed region (every %d%s launch bracketed)" % (ev_stride, "th" if ev_stride > 1 else "st")
-    if not in_region:
-        timed_in = "separate pass of %d steps on ONE stream directly before the warm-up steps (in the timed region itself " \
-                   "kernels of %d boxes share the chip); every launch bracketed" % (prof_steps, nstreams)
-    ms, launches = prof["fft_strided"]
-    # a step holds two strided y passes (inverse and forward), each launched once per x-plane batch (fb_fft_launch.inc
-    # yz_passes): one launch reads and writes its share of N*N*(N/2) complex values (packed work spectrum)
-    ncols = N // 2
-    alg_bytes = 2 * (2.0 * N * N * ncols * 2 * s) * prof_steps / max(plain_launches, 1)
-    achieved = alg_bytes / (ms / max(launches, 1) * 1e-3) / 1e9 if ms > 0 else None
-    fp = from_profiles(N, args.precision)
     line = {
         "metric": "%d^3 box realisations/sec (gen + log-normal + P(k))" % N if not args.gaussian_only
                   else "%d^3 box realisations/sec (gen + P(k), NO log-normal: tuning run)" % N,
@@ -687,17 +685,31 @@ def main():
                                "log-normal transform + binned P(k), nbins=%d" % (N, args.nbins),
                    "nsamp": N, "parallelism": "replicas x%d" % world, "streams_per_gpu": len(boxes),
                    "warmup_steps_run": max(args.warmup, len(boxes)), "spin_up_s": args.spin_up,
-                   "spin_up_steps": spin_steps},
-        "roofline": {"bound": "hbm", "kernel": "k_fft_strided (y FFT pass over a plane batch of the half spectrum)",
-                     "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS if achieved else None,
-                     "traffic": fp["traffic_bytes_per_launch"], "algorithmic_bytes": alg_bytes,
-                     "avg_launch_us": 1e3 * ms / max(launches, 1), "launches": plain_launches,
-                     "launches_timed": launches, "timed_in": timed_in,
-                     "note": "plane batches are sized to the 256 MiB Infinity Cache, so most of these bytes are served "
-                             "on-die: this is L2 <-> fabric bandwidth; the whole-step figure (pipeline_roofline) is the HBM statement"},
-        "from_profiles": fp,
+                   "spin_up_steps": spin_steps, "full": args.full},
+        "roofline": None,                  # several streams without --full: no pass of its own measured the kernel
     }
+    ncols = N // 2
+    if prof is not None:
+        timed_in = "timed region (every %d%s launch bracketed)" % (ev_stride, "th" if ev_stride > 1 else "st")
+        if not in_region:
+            timed_in = "separate pass of %d steps on ONE stream directly before the warm-up steps (in the timed region " \
+                       "itself kernels of %d boxes share the chip); every launch bracketed" % (prof_steps, nstreams)
+        ms, launches = prof["fft_strided"]
+        # a step holds two strided y passes (inverse and forward), each launched once per x-plane batch (fb_fft_launch.inc
+        # yz_passes): one launch reads and writes its share of N*N*(N/2) complex values (packed work spectrum)
+        alg_bytes = 2 * (2.0 * N * N * ncols * 2 * s) * prof_steps / max(plain_launches, 1)
+        achieved = alg_bytes / (ms / max(launches, 1) * 1e-3) / 1e9 if ms > 0 else None
+        fp = from_profiles(N, args.precision)
+        line["roofline"] = {"bound": "hbm", "kernel": "k_fft_strided (y FFT pass over a plane batch of the half spectrum)",
+                            "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                            "frac": achieved / HBM_PEAK_GBS if achieved else None,
+                            "traffic": fp["traffic_bytes_per_launch"], "algorithmic_bytes": alg_bytes,
+                            "avg_launch_us": 1e3 * ms / max(launches, 1), "launches": plain_launches,
+                            "launches_timed": launches, "timed_in": timed_in,
+                            "note": "plane batches are sized to the 256 MiB Infinity Cache, so most of these bytes are "
+                                    "served on-die: this is L2 <-> fabric bandwidth; the whole-step figure "
+                                    "(pipeline_roofline) is the HBM statement"}
+        line["from_profiles"] = fp
     if not in_region:
         half = float(N) * N * (N // 2) * 2 * s                      # one sweep of the packed work spectrum = of the real field
         for key, cls, nbytes, what in (
@@ -743,7 +755,7 @@ def main():
         b.engine.close()
     del boxes
     line.update(extras)
-    if not args.no_extras and world > 1:
+    if args.full and not args.no_extras and world > 1:
         # one box over all ranks, as child jobs (the other ranks of this job have left their GPUs by now)
         out = {}
         torch.cuda.empty_cache()
@@ -771,7 +783,7 @@ def main():
                 out[str(n2)] = {"error": "%s: %s" % (type(e).__name__, e)}
                 failed = True
         line["strong_scaling"] = out
-    if not args.no_cpu_baseline and world == 1:       # rank 0 at N = 1 only
+    if args.full and not args.no_cpu_baseline and world == 1:       # rank 0 at N = 1 only
         line["cpu_baseline"] = cpu_baseline(N, args.cpu_nsamp or (N if N <= 512 else 256), args.nbins)
     else:
         line["cpu_baseline"] = None

@@ -4,6 +4,7 @@ import json
 import os
 import subprocess
 import sys
+import time
 
 import pytest
 
@@ -22,8 +23,10 @@ def _json_lines(text):
 
 
 def test_single_gpu_line():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1000", "--warmup", "2", "--nsamp", "256",
-                        "--cpu-nsamp", "64", "--sizes", "128,512"], capture_output=True, text=True, timeout=900, cwd=ROOT)
+    """--full: the headline and every measurement of its own in the same line."""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "1000", "--warmup", "2",
+                        "--nsamp", "256", "--cpu-nsamp", "64", "--sizes", "128,512"],
+                       capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = _json_lines(r.stdout)
     assert len(lines) == 1
@@ -59,14 +62,44 @@ def test_single_gpu_line():
     assert "best of" in c3["workload"]
 
 
+def test_plain_run_is_the_headline_only():
+    """Without --full the run sets up, spins up, warms up, times the steps and prints the line: none of the legs, passes
+    or baselines that are measurements of their own, and little time outside the timed steps.  With one stream the
+    roofline brackets sit inside the timed region, so that object stays."""
+    base = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "400", "--warmup", "2"]
+    t0 = time.time()
+    r = subprocess.run(base + ["--nsamp", "256"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    wall = time.time() - t0
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = _json_lines(r.stdout)
+    assert len(lines) == 1
+    d = lines[0]
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype",
+                "regions", "config", "pipeline_roofline"):
+        assert key in d, key
+    assert d["steps"] == 400 and d["warmup"] == 2 and d["value"] > 0 and d["unit"] == "boxes/s"
+    assert d["metric"] == "256^3 box realisations/sec (gen + log-normal + P(k))" and d["dtype"] == "f32"
+    assert abs(d["ms_per_step"] * d["value"] - 1e3) < 1e-6 * 1e3 and d["config"]["full"] is False
+    assert d["roofline"] is None and d["cpu_baseline"] is None
+    for key in ("f64", "config3", "spectra_only_variant", "sizes", "strong_scaling", "roofline_gen", "roofline_bin",
+                "roofline_z", "from_profiles"):
+        assert key not in d, key
+    assert wall - (400 + 2) * d["ms_per_step"] * 1e-3 < 30.0, wall
+    r = subprocess.run(base + ["--nsamp", "256", "--streams", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-2000:]
+    d = _json_lines(r.stdout)[0]
+    assert d["roofline"]["timed_in"].startswith("timed region") and d["roofline"]["launches_timed"] >= 1
+    assert "kernel_ms_per_step" in d and "f64" not in d and d["cpu_baseline"] is None
+
+
 def test_two_ranks_started_by_bench_itself():
-    """`python bench.py --gpus 2` with no launcher around it: bench.py starts the two ranks (rehearsal: gloo control
+    """`python bench.py --full --gpus 2` with no launcher around it: bench.py starts the two ranks (rehearsal: gloo control
     flow, both ranks on this one GPU), rank 0 prints the line, and the strong-scaling leg runs the slab-decomposed box
     as a child job of two ranks."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK")}
     env.update(FASTBOX_BENCH_BACKEND="gloo", FASTBOX_BENCH_ONE_DEVICE="1")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "1000", "--warmup", "2",
-                        "--nsamp", "128", "--slab-sizes", "64"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "1000",
+                        "--warmup", "2", "--nsamp", "128", "--slab-sizes", "64"],
                        capture_output=True, text=True, timeout=900, cwd=ROOT, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [d for d in _json_lines(r.stdout) if d.get("scaling") == "weak"]

@@ -6,7 +6,7 @@ echo "test rc $rc"; tail -3 gpurun_out/r4d/test2048.txt
 if [ $rc -ge 124 ]; then exit $rc; fi
 for streams in 2 1; do for mask in 0 1 7; do for pb in 0 4 8 16; do
   if [ $mask = 7 ] && [ $pb != 4 ]; then continue; fi
-  line=$(FB_WIDE_ROWS=$mask timeout -k 10 300 python bench.py --nsamp 2048 --no-extras --no-cpu-baseline --steps 8 --warmup 2 --streams $streams --plane-batch $pb 2>/dev/null | tail -1); rc=$?
+  line=$(FB_WIDE_ROWS=$mask timeout -k 10 300 python bench.py --full --nsamp 2048 --no-extras --no-cpu-baseline --steps 8 --warmup 2 --streams $streams --plane-batch $pb 2>/dev/null | tail -1); rc=$?
   if [ $rc -ge 124 ]; then echo "timeout"; exit $rc; fi
   python - "$line" <<PY | tee -a $OUT
 import json,sys

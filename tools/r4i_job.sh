@@ -2,7 +2,7 @@
 mkdir -p gpurun_out/r4i; OUT=gpurun_out/r4i/z2048.txt; : > $OUT
 for rnd in 1 2; do for v in tw2off default; do
   if [ $v = default ]; then unset FASTBOX_HIP_LIB; else export FASTBOX_HIP_LIB=$PWD/fastbox_amd/lib/variants/lib_$v.so; fi
-  line=$(timeout -k 10 300 python bench.py --nsamp 2048 --no-extras --no-cpu-baseline --steps 8 --warmup 2 --regions 3 2>/dev/null | tail -1); rc=$?
+  line=$(timeout -k 10 300 python bench.py --full --nsamp 2048 --no-extras --no-cpu-baseline --steps 8 --warmup 2 --regions 3 2>/dev/null | tail -1); rc=$?
   if [ $rc -ge 124 ]; then echo timeout; exit $rc; fi
   python - "$line" <<PY | tee -a $OUT
 import json,sys

@@ -11,6 +11,6 @@ done
 for rnd in 1 2; do for v in r32off r32gen r32bin default; do
   if [ $v = default ]; then unset FASTBOX_HIP_LIB; else export FASTBOX_HIP_LIB=$PWD/fastbox_amd/lib/variants/lib_$v.so; fi
   for st in 2 1; do
-  timeout -k 10 300 python bench.py --no-extras --no-cpu-baseline --steps 20 --warmup 5 --streams $st 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('512^3 $v streams $st round $rnd: %.1f boxes/s' % d['value'], d.get('roofline_gen',{}).get('avg_launch_us'), d.get('roofline_bin',{}).get('avg_launch_us'))" | tee -a $OUT
+  timeout -k 10 300 python bench.py --full --no-extras --no-cpu-baseline --steps 20 --warmup 5 --streams $st 2>/dev/null | tail -1 | python -c "import json,sys; d=json.loads(sys.stdin.read()); print('512^3 $v streams $st round $rnd: %.1f boxes/s' % d['value'], d.get('roofline_gen',{}).get('avg_launch_us'), d.get('roofline_bin',{}).get('avg_launch_us'))" | tee -a $OUT
   done
 done; done
