@@ -92,6 +92,11 @@ SIGNATURES = {
     "fb_cola_grid_velocity": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "fb_cola_run": (c_int, [c_void_p, c_void_p, c_int, P_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                             c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fb_watershed": (c_int, [c_void_p, c_void_p, c_int, c_double, c_void_p, c_void_p, ctypes.POINTER(c_i64), c_void_p]),
+    "fb_region_stats": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_void_p, P_i32, c_void_p]),
+    "fb_merge_regions": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_double, c_void_p, ctypes.POINTER(c_i64), c_void_p]),
+    "fb_stack_voids": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, P_double, c_void_p, c_int, c_void_p,
+                               c_void_p, c_void_p, c_void_p]),
     "fb_real_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_void_p]),
     "fb_real_multiply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fb_real_to_complex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),

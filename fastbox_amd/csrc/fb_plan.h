@@ -97,6 +97,11 @@ struct fb_plan {
     void* halo_acc = nullptr;         // grown on demand
     size_t halo_acc_cap = 0;          // bytes
 
+    // void finding (fb_voids.hip): flags and reduction partials, and the per-label / per-tile work tables
+    void* void_small = nullptr;       // [FB_VOID_SMALL] bytes
+    void* void_work = nullptr;        // grown on demand
+    size_t void_work_cap = 0;         // bytes
+
     // second stream for alternate plane batches of the y/z passes (created on first use)
     hipStream_t aux_stream = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;

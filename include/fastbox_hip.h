@@ -318,6 +318,41 @@ int fb_cola_grid_velocity(fb_plan* plan, void* num_inout, const void* count, voi
 int fb_cola_run(fb_plan* plan, const void* delta0, int n_steps, const double* coef, double* pos, void* psi1, void* psi2, void* pres,
                 void* force, void* count, void* delta, void* work_half1, void* work_half2, void* stream);
 
+/* ---- void finding (fastbox/voids.py, examples/example_void_detection.py; definitions in DESIGN.md section 4) ---------------
+ * One box on one GPU.  Labels are DEVICE int32[N^3] in C order; neighbours are the 6 face neighbours; the box is not periodic.
+ * fb_watershed: steepest descent on the strict order (f, i), f as stored: every voxel inside the mask points to the least of
+ *   itself and its in-mask face neighbours; the pointers are followed to their root (a minimum); label = 1 + the rank of the
+ *   root among all minima in raster order, 0 outside the mask.  Inside: f finite and, by mask_kind, FB_VOID_MASK_ALL: always;
+ *   _THRESHOLD: (double) f <= mask_threshold; _U8: mask (DEVICE uint8[N^3]) != 0; _FIELD: mask (DEVICE field of the plan's
+ *   precision) != 0.  *n_regions = the number of minima.  Synchronises (one read-back per pointer-jumping round).
+ * fb_region_stats: per label l = 0..n_labels, stats_out (DEVICE, 11 columns of n_labels + 1 eight-byte words): int64 count,
+ *   arg-min in (f, i) order (-1: none), sums of ix, iy, iz; double sum f, sum w, sums of w ix, w iy, w iz (w = max(-f, 0)),
+ *   mean f = sum f / count.  field NULL: counts and index sums only.  A non-finite voxel of label 0 adds to its count and index
+ *   sums only.  The double sums are fixed-point accumulations, the same bit for bit from call to call.  *bad |= 1 if field is
+ *   not finite in a voxel of label >= 1, |= 2 if a label lies outside 0..n_labels.  Synchronises.
+ * fb_merge_regions: labels_out = the connected components of the graph whose nodes are the labels >= 1 and whose edges join
+ *   face-neighbouring labels i != j with |means[i] - means[j]| < threshold (means: DEVICE double[n_labels + 1]), numbered
+ *   1..M in the order of their least label; 0 stays 0.  *n_merged = M.  Synchronises (one read-back per round).
+ * fb_stack_voids: void v has label void_labels[v] and geom[4 v .. 4 v + 3] = centre x, y, z and radius (DEVICE).  Its point
+ *   (a, b, c) is p = centre + radius (grid[b], grid[a], grid[c]) (grid: DEVICE double[grid_pix]), u = (p - axes[0, 2, 4]) /
+ *   axes[1, 3, 5] per axis (axes: HOST x0, dx, y0, dy, z0, dz); it is valid if the 8 voxels floor(u) + {0, 1}^3 lie in the
+ *   box and carry the void's label, and the trilinear value of field there is finite.  mean_out (DEVICE double[grid_pix^3]):
+ *   the mean over the voids of the valid values (NaN: none); count_out (DEVICE int64): their number; hit_out[v] (DEVICE
+ *   int32): 1 if void v has a valid point.  Sums in a fixed order.  Asynchronous.                                           */
+#define FB_VOID_MASK_ALL 0
+#define FB_VOID_MASK_THRESHOLD 1
+#define FB_VOID_MASK_U8 2
+#define FB_VOID_MASK_FIELD 3
+int fb_watershed(fb_plan* plan, const void* field, int mask_kind, double mask_threshold, const void* mask, int32_t* labels_out,
+                 int64_t* n_regions, void* stream);
+int fb_region_stats(fb_plan* plan, const int32_t* labels, int64_t n_labels, const void* field, void* stats_out, int* bad,
+                    void* stream);
+int fb_merge_regions(fb_plan* plan, const int32_t* labels, int64_t n_labels, const double* means, double threshold,
+                     int32_t* labels_out, int64_t* n_merged, void* stream);
+int fb_stack_voids(fb_plan* plan, const int32_t* labels, const void* field, const int32_t* void_labels, const double* geom,
+                   int64_t n_voids, const double* axes, const double* grid, int grid_pix, double* mean_out, int64_t* count_out,
+                   int32_t* hit_out, void* stream);
+
 /* ---- transfer functions (apply_transfer_fn box.py:374-379, smooth_field :651-653) ---------- */
 #define FB_FILT_TABLE 0          /* table: real multiplier, same layout as the field */
 #define FB_FILT_BEAM_HIGHPASS 1  /* (1-exp(-.5(|kpar|/p0)^p2)) [p0>0] * exp(-.5(kperp/p1)^2) [p1>0] */
