@@ -700,6 +700,8 @@ int fb_watershed(fb_plan* p, const void* field, int mask_kind, double mask_thres
     FB_REQUIRE(!p->comm, "void finding runs on one box on one GPU");
     FB_REQUIRE(mask_kind >= FB_VOID_MASK_ALL && mask_kind <= FB_VOID_MASK_FIELD, "mask_kind must be FB_VOID_MASK_ALL .. _FIELD");
     FB_REQUIRE(mask_kind < FB_VOID_MASK_U8 || mask, "mask: null device pointer");
+    FB_REQUIRE((unsigned long long)p->N * p->N * p->N < (unsigned long long)FB_VOID_ROOT,
+               "watershed: N^3 must be below 2^31 (N <= 1290): a parent word holds a voxel index in 31 bits");
     FB_USE_DEVICE(p);
     hipStream_t s = (hipStream_t)stream;
     return FB_DISPATCH(p, watershed<float>(p, field, mask_kind, mask_threshold, mask, (unsigned*)labels_out, n_regions, s),

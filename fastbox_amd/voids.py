@@ -26,6 +26,7 @@ MASK_ALL, MASK_THRESHOLD, MASK_U8, MASK_FIELD = 0, 1, 2, 3        # FB_VOID_MASK
 NCOL = 11                                                           # columns of fb_region_stats
 KINDS = ("uniform", "minimum", "density")
 MAX_LABEL = 2 ** 30
+MAX_WATERSHED_N = 1290                                              # N^3 < 2^31: bit 31 of a parent word marks a root
 
 
 class VoidLabels(object):
@@ -184,6 +185,9 @@ def _cat(void_cat, n_labels):
 
 
 def _watershed(eng, f, kind, thr, mask_ptr):
+    if eng.N ** 3 >= 2 ** 31:
+        raise ValueError("watershed: N^3 must be below 2^31 (N <= %d), got N = %d: a parent word holds a voxel index in 31 bits"
+                         % (MAX_WATERSHED_N, eng.N))
     buf = eng._alloc_bytes(4 * eng.N ** 3)
     n = ctypes.c_int64(0)
     _lib.call("fb_watershed", eng._plan, f.ptr, kind, float(thr), mask_ptr, buf.ptr, ctypes.byref(n), eng.stream)
@@ -194,7 +198,8 @@ def watershed(field, markers=None, mask=None, box=None):
     """skimage.segmentation.watershed(field, markers=None, mask=mask) as the example calls it: steepest descent on (f, i), one
     region per local minimum, labels 1..n in the raster order of the minima, 0 outside the mask.  ``field``: a real DeviceArray
     of a box, or a host (N, N, N) array with ``box=`` (uploaded in the box's precision).  ``mask``: None (every finite voxel),
-    a host boolean array or a real DeviceArray (nonzero = inside); non-finite voxels are always outside.  Returns VoidLabels."""
+    a host boolean array or a real DeviceArray (nonzero = inside); non-finite voxels are always outside.  N^3 < 2^31, i.e.
+    N <= 1290 (a parent word holds a voxel index in 31 bits, bit 31 marks a root): ValueError beyond.  Returns VoidLabels."""
     _check_markers(markers)
     eng = _engine(field, box, "field")
     N = eng.N

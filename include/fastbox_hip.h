@@ -324,7 +324,8 @@ int fb_cola_run(fb_plan* plan, const void* delta0, int n_steps, const double* co
  *   itself and its in-mask face neighbours; the pointers are followed to their root (a minimum); label = 1 + the rank of the
  *   root among all minima in raster order, 0 outside the mask.  Inside: f finite and, by mask_kind, FB_VOID_MASK_ALL: always;
  *   _THRESHOLD: (double) f <= mask_threshold; _U8: mask (DEVICE uint8[N^3]) != 0; _FIELD: mask (DEVICE field of the plan's
- *   precision) != 0.  *n_regions = the number of minima.  Synchronises (one read-back per pointer-jumping round).
+ *   precision) != 0.  *n_regions = the number of minima.  N^3 < 2^31 (N <= 1290), since a parent word holds a voxel index
+ *   in 31 bits: FB_ERR_INVALID beyond.  Synchronises (one read-back per pointer-jumping round).
  * fb_region_stats: per label l = 0..n_labels, stats_out (DEVICE, 11 columns of n_labels + 1 eight-byte words): int64 count,
  *   arg-min in (f, i) order (-1: none), sums of ix, iy, iz; double sum f, sum w, sums of w ix, w iy, w iz (w = max(-f, 0)),
  *   mean f = sum f / count.  field NULL: counts and index sums only.  A non-finite voxel of label 0 adds to its count and index

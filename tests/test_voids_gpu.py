@@ -54,13 +54,10 @@ def _same_bits(a, b):
         assert getattr(a, k).tobytes() == getattr(b, k).tobytes(), k
 
 
-@pytest.mark.parametrize("prec", PRECS)
-@pytest.mark.parametrize("N,scale", [(16, CUBE), (32, CUBE), (48, CUBE), (64, CUBE), (64, CUBOID)])
-def test_watershed_statistics_catalogue_stacking(prec, N, scale):
-    box = _box(N, prec, scale)
-    d = box.realise_density()
-    f = _stored(box, d)
-    lab = voids.watershed(d, markers=None)
+def _check_chain(box, d, f, scale, grid_pixes=(15,)):
+    """Watershed, statistics, catalogue and stacking of the field d (a device field of the box, or a host array), whose stored
+    values are f, against the numpy statement."""
+    lab = voids.watershed(d, markers=None, box=box)
     ref, n = vn.watershed(f, vn.inside(f))
     _check_labels(lab, ref, n)
     st = voids.region_statistics(lab, d)
@@ -82,16 +79,42 @@ def test_watershed_statistics_catalogue_stacking(prec, N, scale):
     # stacking, on the device's own centres and radii
     cen = voids.void_centroids(cat, lab, box)
     rad = voids.void_radii_array(cat, lab, box)
-    stk, fail, cnt = voids.stack_voids_at(cat, lab, box, d, cen, rad, grid_pix=15)
-    o, ofail, ocnt = vn.stack(ref, f, cat, cen, rad, box, 1., 15)
+    for pix in grid_pixes:
+        stk, fail, cnt = voids.stack_voids_at(cat, lab, box, d, cen, rad, grid_pix=pix)
+        o, ofail, ocnt = vn.stack(ref, f, cat, cen, rad, box, 1., pix)
+        _check_stack(stk, fail, cnt, o, ofail, ocnt)
+        assert (~np.ma.getmaskarray(o)).any()
+        s2, f2 = voids.stack_voids(cat, lab, box, d, grid_pix=pix)
+        assert s2.data.tobytes() == stk.data.tobytes() and f2 == fail
+    return n
+
+
+def _check_stack(stk, fail, cnt, o, ofail, ocnt):
     np.testing.assert_array_equal(cnt, ocnt)
     np.testing.assert_array_equal(np.ma.getmaskarray(stk), np.ma.getmaskarray(o))
     assert [int(x) for x in fail] == [int(x) for x in ofail]
     m = ~np.ma.getmaskarray(o)
-    assert m.any()
     np.testing.assert_allclose(stk.data[m], o.data[m], rtol=1e-10, atol=1e-12)
-    s2, f2 = voids.stack_voids(cat, lab, box, d, grid_pix=15)
-    assert s2.data.tobytes() == stk.data.tobytes() and f2 == fail
+
+
+def _check_apply_merge(box, d, f):
+    """apply_watershed at a merge threshold of 0.3 sigma against the numpy statement; returns (regions, merged regions)."""
+    mth = 0.3 * float(np.std(f))
+    out = voids.apply_watershed(d, mask_threshold=0., merge_threshold=mth, verbose=False, box=box)
+    ref, n = vn.watershed(f, vn.inside(f, threshold=0.))
+    rs = vn.region_stats(ref, n, f)
+    mref, M = vn.merge(ref, n, rs["mean"], mth, margin=1e-6)
+    assert 0 < M < n
+    _check_labels(out, mref, M)
+    return n, M
+
+
+@pytest.mark.parametrize("prec", PRECS)
+@pytest.mark.parametrize("N,scale", [(16, CUBE), (32, CUBE), (48, CUBE), (64, CUBE), (64, CUBOID)])
+def test_watershed_statistics_catalogue_stacking(prec, N, scale):
+    box = _box(N, prec, scale)
+    d = box.realise_density()
+    _check_chain(box, d, _stored(box, d), scale)
 
 
 @pytest.mark.parametrize("prec", PRECS)
@@ -149,14 +172,7 @@ def test_plateaus_masks_nans(prec):
 def test_apply_watershed_merges_as_the_oracle(prec, N, scale):
     box = _box(N, prec, scale, seed=2)
     d = box.realise_density()
-    f = _stored(box, d)
-    mth = 0.3 * float(np.std(f))
-    out = voids.apply_watershed(d, mask_threshold=0., merge_threshold=mth, verbose=False)
-    ref, n = vn.watershed(f, vn.inside(f, threshold=0.))
-    rs = vn.region_stats(ref, n, f)
-    mref, M = vn.merge(ref, n, rs["mean"], mth, margin=1e-6)
-    assert 0 < M < n
-    _check_labels(out, mref, M)
+    _check_apply_merge(box, d, _stored(box, d))
 
 
 @pytest.mark.parametrize("prec", PRECS)
