@@ -107,6 +107,15 @@ SIGNATURES = {
     "fb_channel_covariance": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fb_leading_eigenvectors": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fb_pca_clean": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
+    "fb_real_min": (c_int, [c_void_p, c_void_p, P_double, ctypes.POINTER(c_i64), c_void_p]),
+    "fb_complex_to_real": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fb_nmf_sweep": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, P_double, c_void_p]),
+    "fb_nmf_residual": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, P_double, c_void_p]),
+    "fb_nndsvd_norms": (c_int, [c_void_p, c_void_p, c_int, P_double, c_void_p]),
+    "fb_nndsvd_fill": (c_int, [c_void_p, c_void_p, c_int, P_double, c_int, c_double, c_double, c_void_p]),
+    "fb_rotated_covariance": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fb_ica_step": (c_int, [c_void_p, P_double, c_void_p, c_int, c_int, c_double, P_double, P_double, c_void_p]),
+    "fb_ica_sources": (c_int, [c_void_p, P_double, P_double, c_void_p, c_int, c_void_p, P_double, c_void_p]),
     "fb_sky_realise_map": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_double, c_void_p, c_void_p, c_void_p]),
     "fb_sky_normal_map": (c_int, [c_void_p, c_void_p, c_u64, c_double, c_double, c_void_p, c_void_p]),
     "fb_sky_gaussian_filter": (c_int, [c_void_p, c_void_p, c_void_p, P_double, c_int, c_void_p]),

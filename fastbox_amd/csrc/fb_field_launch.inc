@@ -470,17 +470,6 @@ int FBI(real_axpby)(fb_plan* p, const void* x, const void* y, void* out, double 
 }
 
 // ---- PCA foreground cleaning (kernels: fb_field_kernels.h, last section) -----------------------------------------
-namespace {
-int ensure_bytes(void** buf, size_t* cap, size_t need) {
-    if (*cap >= need) return FB_OK;
-    if (*buf) FB_HIP(hipFree(*buf));
-    *buf = nullptr; *cap = 0;
-    FB_HIP(hipMalloc(buf, need));
-    *cap = need;
-    return FB_OK;
-}
-}  // namespace
-
 // mean_dev[N] (device, fp64) = mean over the N^2 pixels of every channel (filters.py:142)
 int FBI(channel_means)(fb_plan* p, const void* cube, double* mean_dev, hipStream_t s) {
     const int N = p->N;

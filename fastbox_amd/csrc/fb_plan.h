@@ -149,6 +149,15 @@ void fb_set_error(const std::string& msg);
 int fb_hip_check(hipError_t e, const char* what);
 #define FB_HIP(x) do { int _r = fb_hip_check((x), #x); if (_r) return _r; } while (0)
 #define FB_LAUNCH_CHECK(name) do { int _r = fb_hip_check(hipGetLastError(), name); if (_r) return _r; } while (0)
+// grow-only device work buffer (the plan's pca_work and its like): the one policy for everything that shares such a buffer
+static inline int ensure_bytes(void** buf, size_t* cap, size_t need) {
+    if (*cap >= need) return FB_OK;
+    if (*buf) FB_HIP(hipFree(*buf));
+    *buf = nullptr; *cap = 0;
+    FB_HIP(hipMalloc(buf, need));
+    *cap = need;
+    return FB_OK;
+}
 
 // ---- per-precision launchers (fb_fft_launch.inc, fb_field_launch.inc) ------------
 #define FB_DECL(sfx) \

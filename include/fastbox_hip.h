@@ -460,6 +460,53 @@ int fb_leading_eigenvectors(fb_plan* plan, const double* cov_dev, int nmodes, do
 int fb_pca_clean(fb_plan* plan, const void* cube, const double* mean_dev, const double* modes_dev, int nmodes,
                  void* cube_out, double* amps_dev, void* stream);
 
+/* ---- NMF and ICA foreground cleaning (fastbox/filters.py:373-432, :187-243) ----
+ * The cube is T[N][N][N] in the plan's precision, frequency last; all other state is fp64.  W_dev[k][N^2] and X1_dev[n][N^2]
+ * have the layout of fb_pca_clean's amps_dev; H_dev[k][N] holds one component's spectrum contiguously.  1 <= k, n <= 16
+ * (FB_ERR_INVALID otherwise).  Every sum is taken in a fixed order without atomics: results are bitwise repeatable.
+ *
+ * fb_real_min: *min_out = the least value of a real cube (NaN is skipped), *nonfinite_out = the number of NaN / infinite
+ *   values: the admissibility test of NMF without a download.  Synchronises.
+ * fb_complex_to_real: real_cube = Re full_cube (complex<T>[N][N][N] -> T[N][N][N]).                                       */
+int fb_real_min(fb_plan* plan, const void* cube, double* min_out, int64_t* nonfinite_out, void* stream);
+int fb_complex_to_real(fb_plan* plan, const void* full_cube, void* real_cube, void* stream);
+/* fb_nmf_sweep: ONE iteration of scikit-learn's coordinate-descent solver (Frobenius loss, no regularisation, no shuffling)
+ *   for X ~ W H, X[N^2][N] = the cube: with H H^T and X H^T every row of W is swept cyclically,
+ *     grad = -(X H^T)[i][t] + sum_r (H H^T)[t][r] W[i][r];  violation += |grad|, or |min(0, grad)| where W[i][t] == 0;
+ *     W[i][t] = max(W[i][t] - grad / (H H^T)[t][t], 0) unless that diagonal entry is 0,
+ *   then the rows of H^T likewise with W^T W and X^T W of the new W.  The cube is read once: the pass that sweeps a pixel's
+ *   row of W also adds the pixel to X^T W and W^T W.  W_dev and H_dev are updated in place; violation_out[2] (host) = the
+ *   violations of the W half and of the H half.  N <= 1024 (FB_ERR_UNSUPPORTED beyond).  Synchronises.
+ * fb_nmf_residual: cube_out = X - W H (may be NULL), *sumsq_out (host; may be NULL) = ||X - W H||_F^2 in fp64; synchronises
+ *   if sumsq_out is given.
+ * fb_nndsvd_norms: out[2 j], out[2 j + 1] (host) = the sums of squares of the positive and of the negative entries of
+ *   row j of amps_dev[k][N^2] (the NNDSVD rule needs the norms of both parts of every singular vector).  Synchronises.
+ * fb_nndsvd_fill: amps_dev[j][p] <- max(coef[j] amps_dev[j][p], 0) (row 0: the absolute value if abs_first), then every value
+ *   below eps becomes `fill` (NNDSVDA: the mean of X).  coef[k] on the host.
+ * fb_rotated_covariance: cov_dev[N][N] = B^T B / (N^2 - 1) for B[p][m] = sum_c Vt_dev[m][c] X[p][c], the spectra in the basis
+ *   of the N rows of Vt_dev[N][N] (fp64), formed and kept in fp64 for both plans and not centred.  With Vt the eigenvectors of
+ *   X^T X, B has nearly orthogonal columns, so that the singular values and vectors of X follow from this matrix without the
+ *   loss of the Gram matrix.  work_dev: N^3 + N doubles.                                              */
+int fb_nmf_sweep(fb_plan* plan, const void* cube, double* W_dev, double* H_dev, int k, double* violation_out, void* stream);
+int fb_nmf_residual(fb_plan* plan, const void* cube, const double* W_dev, const double* H_dev, int k, void* cube_out,
+                    double* sumsq_out, void* stream);
+int fb_nndsvd_norms(fb_plan* plan, const double* amps_dev, int k, double* out, void* stream);
+int fb_nndsvd_fill(fb_plan* plan, double* amps_dev, int k, const double* coef, int abs_first, double eps, double fill,
+                   void* stream);
+int fb_rotated_covariance(fb_plan* plan, const void* cube, const double* Vt_dev, double* work_dev, double* cov_dev, void* stream);
+/* fb_ica_step: the sums of one FastICA fixed-point step (algorithm 'parallel') for the unmixing matrix W[n][n] (host) and
+ *   the whitened data X1_dev: G_out[n][n] = g(W X1) X1^T / N^2 and gp_out[n] = mean over pixels of g'((W X1)_i) (host), with
+ *   g = tanh(alpha y) (FB_ICA_LOGCOSH), y exp(-y^2 / 2) (FB_ICA_EXP) or y^3 (FB_ICA_CUBE).  Synchronises.
+ * fb_ica_sources: sources_dev[i][p] = scale[i] (W X1)[i][p]; moments_out[2 n] (host; may be NULL) = the mean over pixels of
+ *   every row of sources_dev, then the mean of its square.  W[n][n], scale[n] on the host.  Synchronises.                  */
+#define FB_ICA_LOGCOSH 0
+#define FB_ICA_EXP 1
+#define FB_ICA_CUBE 2
+int fb_ica_step(fb_plan* plan, const double* W, const double* X1_dev, int n, int fun, double alpha, double* G_out,
+                double* gp_out, void* stream);
+int fb_ica_sources(fb_plan* plan, const double* W, const double* scale, const double* X1_dev, int n, double* sources_dev,
+                   double* moments_out, void* stream);
+
 /* ---- the steps after the density-field path: foregrounds (fastbox/foregrounds.py:48-175) and radiometer
  * noise (fastbox/noise.py:25-75).  2-D maps are T[N][N] over (x, y); cubes T[N][N][N], frequency axis last. ---- */
 /* realise_foreground_amp (:99-107): map_out = Re ifft2((re + i im) amp2d) + monopole.  amp2d = sqrt(C_ell) per
