@@ -12,6 +12,8 @@ from .transfer import BeamHighpass, Wedge         # noqa: F401
 from .device import DeviceArray                   # noqa: F401
 from .sky import ForegroundModel, NoiseModel      # noqa: F401
 from . import filters                             # noqa: F401
+from . import inpaint                             # noqa: F401
+from . import analysis                            # noqa: F401
 from . import montecarlo                          # noqa: F401
 from .beams import BeamModel                      # noqa: F401
 from .halos import HaloDistribution, HaloCatalogue, ColaParticles   # noqa: F401

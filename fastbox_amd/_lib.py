@@ -116,6 +116,14 @@ SIGNATURES = {
     "fb_rotated_covariance": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fb_ica_step": (c_int, [c_void_p, P_double, c_void_p, c_int, c_int, c_double, P_double, P_double, c_void_p]),
     "fb_ica_sources": (c_int, [c_void_p, P_double, P_double, c_void_p, c_int, c_void_p, P_double, c_void_p]),
+    "fb_los_matmul": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fb_gcr_rhs": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_u64, c_u64, c_void_p, c_void_p,
+                           c_void_p, c_void_p, c_void_p]),
+    "fb_gcr_solve": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_int, c_void_p,
+                             P_double, c_void_p]),
+    "fb_gcr_finish": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_u64, c_u64, c_void_p,
+                              c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "fb_replace_nan_channel_mean": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fb_sky_realise_map": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_double, c_void_p, c_void_p, c_void_p]),
     "fb_sky_normal_map": (c_int, [c_void_p, c_void_p, c_u64, c_double, c_double, c_void_p, c_void_p]),
     "fb_sky_gaussian_filter": (c_int, [c_void_p, c_void_p, c_void_p, P_double, c_int, c_void_p]),

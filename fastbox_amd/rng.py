@@ -52,6 +52,17 @@ def box_muller(a, b, dtype=np.float64):
     # the device's sine / cosine take the angle in revolutions (v_sin_f32, sincospi), i.e. they see u2 itself: the
     # angle is formed in double here -- 2 pi rounded to float32 is 2.8e-8 too large, which would bias cos by that
     # much on average and, summed coherently over 10^8 modes, put a spike at the origin of a 512^3 field
+    if np.dtype(dtype) == np.float64:
+        # to rounding, as sincospi is: 2 u2 = n / 2 + t with |t| <= 1/4 exactly (u2 is a dyadic number), so that the one
+        # rounding of pi t is relative to a small angle; 2 pi u2 rounded as a whole is off by up to 1.4e-15 in the angle
+        x = 2.0 * u2
+        n = np.rint(2.0 * x)
+        th = np.pi * (x - 0.5 * n)
+        c0, s0 = np.cos(th), np.sin(th)
+        q = n.astype(np.int64) & 3
+        c = np.where(q == 0, c0, np.where(q == 1, -s0, np.where(q == 2, -c0, s0)))
+        sn = np.where(q == 0, s0, np.where(q == 1, c0, np.where(q == 2, -s0, -c0)))
+        return r * c, r * sn
     ang = 2.0 * np.pi * u2.astype(np.float64)
     return (r * np.cos(ang).astype(dtype)).astype(dtype), (r * np.sin(ang).astype(dtype)).astype(dtype)
 
@@ -105,6 +116,14 @@ def stream_normals(n, stream, seed, realisation=0, dtype=np.float64):
 def los_noise(N, seed, dtype=np.float64):
     """Standard normals n(i,j,m) of the redshift-space small-scale velocities (stream 1)."""
     return stream_normals(N ** 3, 1, seed, 0, dtype).reshape(N, N, N)
+
+
+def gcr_normals(N, which, seed, realisation=0):
+    """The unit normals of the constrained realisations (fb_inpaint.hip): which = 1, 2, 3 for omega1, omega2, omega3 on streams
+    7, 8, 9; element p N + c of the stream belongs to line of sight p, channel c.  Always fp64.  Returns (N^2, N)."""
+    if which not in (1, 2, 3):
+        raise ValueError("which: 1 (omega1), 2 (omega2) or 3 (omega3)")
+    return stream_normals(N ** 3, 6 + which, seed, realisation, np.float64).reshape(N * N, N)
 
 
 # ---- halo tracers (fb_halo.hip): Poisson counts on stream 5, catalogue scatter on stream 6 ----------------------------

@@ -507,6 +507,53 @@ int fb_ica_step(fb_plan* plan, const double* W, const double* X1_dev, int n, int
 int fb_ica_sources(fb_plan* plan, const double* W, const double* scale, const double* X1_dev, int n, double* sources_dev,
                    double* moments_out, void* stream);
 
+/* ---- in-painting of flagged channels by Gaussian constrained realisations (fastbox/inpaint.py:35-155), fb_inpaint.hip ----
+ * For every line of sight p (a row of the (N^2, N) view of the cube) with flags w, diagonal noise variance sigma^2, signal
+ * prior S and q = w^2 / sigma^2:  A_p x_p = b_p,  A_p = I + S^(1/2) diag(q_p) S^(1/2),
+ * b_p = S^(1/2) (q_p d_p + sqrt(q_p) omega2) + omega1,  s_p = S^(1/2) x_p  (DESIGN.md section 4).  Cubes called fp64 below are
+ * double[N^2][N] on the DEVICE whatever the plan's precision; N <= 1024.
+ *
+ * fb_los_matmul: Y[p][a] = post[p][a] sum_b M_dev[a][b] (pre[p][b] X[p][b]) + add[p][a] on the fp64 matrix cores
+ *   (v_mfma_f64_16x16x4_f64).  M_dev[N][N] fp64, not assumed symmetric.  X: a cube in the plan's precision (FB_LOS_X_PLAN) or
+ *   fp64 (FB_LOS_X_FP64); pre, post, add: fp64 cubes or NULL; Y: fp64 cube, distinct from X and pre (add == Y is allowed).
+ * fb_gcr_rhs: q_out = w^2 / var (exactly 0 where w = 0), u_out = q d + sqrt(q) omega2 (0 where w = 0: d is selected, not
+ *   multiplied, so a NaN under a flag is legal).  d: cube in the plan's precision.  w: such a cube (FB_GCR_PER_VOXEL) or
+ *   double[N] on the device (FB_GCR_PER_CHANNEL); var: double[N] on the device (FB_GCR_PER_CHANNEL) or a cube in the plan's
+ *   precision (FB_GCR_PER_VOXEL).  draws: FB_GCR_DRAWS_NONE (omega = 0: the Wiener filter), FB_GCR_DRAWS_GIVEN (omega2: fp64
+ *   cube of unit normals; omega1 stays with the caller) or FB_GCR_DRAWS_DEVICE (element p N + c of Philox streams 7 (omega1,
+ *   written to omega1_out) and 8 (omega2) under (seed, realisation)).  qmean_dev[N] (device; may be NULL): the mean of q over
+ *   the pixels of every channel, summed as fb_channel_means does.
+ * fb_gcr_solve: batched preconditioned conjugate gradients from x = 0 over all N^2 rows for A x = b with the preconditioner
+ *   P_dev[N][N] (symmetric positive definite; NULL: none).  A row stops once its recurrence residual |r| <= tol |b| and is
+ *   then left alone; a row with b = 0 takes no iteration.  The loop ends when no row is active or after maxiter iterations;
+ *   one count is read back per iteration.  work: 5 N^3 doubles (4 N^3 without P_dev).  n_iter_dev[N^2]: iterations per row.
+ *   info_out[4] (host): max_p |b - A x| / |b| from one more application of A, the number of rows that met the tolerance,
+ *   the largest iteration count of a row, the iterations of the loop.  Synchronises.
+ * fb_gcr_finish: cube_out = S^(1/2) x (s_work: fp64 scratch cube, not x) + sqrt(var) omega3 (noise: FB_GCR_DRAWS_NONE, _GIVEN
+ *   with omega3 an fp64 cube, or _DEVICE: Philox stream 9), stored in the plan's precision; with `inpaint`, d where w != 0
+ *   (bit for bit) and that value elsewhere.
+ * fb_replace_nan_channel_mean: cube_out = cube with every NaN replaced by the mean of its channel over the voxels that are
+ *   not NaN (fp64 sums in a fixed order; a channel without such a voxel stays NaN; other voxels are copied bit for bit).
+ *   mean_dev[N] (device; may be NULL) receives the means.  cube_out == cube is allowed.                                      */
+#define FB_LOS_X_PLAN 0
+#define FB_LOS_X_FP64 1
+#define FB_GCR_PER_CHANNEL 0
+#define FB_GCR_PER_VOXEL 1
+#define FB_GCR_DRAWS_NONE 0
+#define FB_GCR_DRAWS_GIVEN 1
+#define FB_GCR_DRAWS_DEVICE 2
+int fb_los_matmul(fb_plan* plan, const double* M_dev, const void* X, int x_kind, const double* pre, const double* post,
+                  const double* add, double* Y, void* stream);
+int fb_gcr_rhs(fb_plan* plan, const void* d, const void* w, int w_kind, const void* var, int var_kind, const double* omega2,
+               int draws, uint64_t seed, uint64_t realisation, double* q_out, double* u_out, double* omega1_out, double* qmean_dev,
+               void* stream);
+int fb_gcr_solve(fb_plan* plan, const double* sqrtS_dev, const double* P_dev, const double* q, const double* b, double* x,
+                 double* work, double tol, int maxiter, int32_t* n_iter_dev, double* info_out, void* stream);
+int fb_gcr_finish(fb_plan* plan, const double* sqrtS_dev, const double* x, double* s_work, const void* var, int var_kind,
+                  const double* omega3, int noise, uint64_t seed, uint64_t realisation, const void* d, const void* w, int w_kind,
+                  int inpaint, void* cube_out, void* stream);
+int fb_replace_nan_channel_mean(fb_plan* plan, const void* cube, void* cube_out, double* mean_dev, void* stream);
+
 /* ---- the steps after the density-field path: foregrounds (fastbox/foregrounds.py:48-175) and radiometer
  * noise (fastbox/noise.py:25-75).  2-D maps are T[N][N] over (x, y); cubes T[N][N][N], frequency axis last. ---- */
 /* realise_foreground_amp (:99-107): map_out = Re ifft2((re + i im) amp2d) + monopole.  amp2d = sqrt(C_ell) per
