@@ -12,8 +12,10 @@ the reference's order (``np.random.seed(s)`` gives the reference's counts and ca
 streams 5 (counts) and 6 (catalogue offsets) on the device, reproduced by ``fastbox_amd.rng`` (``stream_poisson``,
 ``scatter_uniforms``).
 
-Limits: an expected count above 2^24 raises ValueError (fp32 counts stay exact).  An all-zero count field gives an empty
-(0, 3) catalogue, where the reference raises.
+Limits: an expected count above 2^24 raises ValueError, so that fp32 counts stay exact; a count drawn above 2^24 -- possible
+from an expected count some 15-20 thousand below the limit, sigma being 4096 there -- is stored rounded to fp32, to an even
+number, on a single-precision plan.  An
+all-zero count field gives an empty (0, 3) catalogue, where the reference raises.
 """
 import ctypes
 

@@ -1,6 +1,9 @@
 """numpy statement of the COLA particle mesh (CosmoBox.realise_density_cola): numpy FFTs, CIC painting with
-np.add.at at fb_paint's nodes, the coefficients of fastbox_amd.cola.  fp64 throughout."""
+np.add.at at fb_paint's nodes, the coefficients of fastbox_amd.cola.  fp64 throughout, unless a stage is given ``dtype``: the
+type the device stores Psi1, Psi2, p_res, F, count and delta in.  Every stored value is then rounded to it once, where the
+device stores, the transforms run in it (scipy.fft keeps float32) and everything else stays fp64, as on the device."""
 import numpy as np
+import scipy.fft
 
 from fastbox_amd import cola
 
@@ -31,19 +34,34 @@ def _mult(N, L, a, b=None, coef=1.0):
     return r
 
 
-def kfield(dk, L, a, b=None, coef=1.0):
+def stored(x, dtype=np.float64):
+    """x rounded once to the stored type, as fp64."""
+    return np.asarray(x, dtype=np.float64).astype(dtype).astype(np.float64)
+
+
+def _fftn(x, dtype):
+    if np.dtype(dtype) == np.float64:
+        return np.fft.fftn(x)
+    return scipy.fft.fftn(np.asarray(x, dtype=np.float32))             # complex64
+
+
+def kfield(dk, L, a, b=None, coef=1.0, dtype=np.float64):
     N = dk.shape[0]
-    return np.fft.ifftn(_mult(N, L, a, b, coef) * dk).real
+    if np.dtype(dtype) == np.float64:
+        return np.fft.ifftn(_mult(N, L, a, b, coef) * dk).real
+    prod = (_mult(N, L, a, b, coef) * dk.astype(np.complex128)).astype(np.complex64)    # the multiplier is fp64, stored
+    return scipy.fft.ifftn(prod).real.astype(np.float64)
 
 
-def lpt(delta0, L):
+def lpt(delta0, L, dtype=np.float64):
     """(Psi1, Psi2), each (3, N, N, N)."""
-    dk = np.fft.fftn(delta0)
-    psi1 = np.array([kfield(dk, L, c) for c in range(3)])
-    xx, yy, zz, xy, xz, yz = [kfield(dk, L, a, b) for a, b in ((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))]
+    dk = _fftn(stored(delta0, dtype), dtype)
+    psi1 = np.array([kfield(dk, L, c, dtype=dtype) for c in range(3)])
+    xx, yy, zz, xy, xz, yz = [kfield(dk, L, a, b, dtype=dtype)
+                              for a, b in ((0, 0), (1, 1), (2, 2), (0, 1), (0, 2), (1, 2))]
     S = ((((xx * yy + xx * zz) + yy * zz) - xy * xy) - xz * xz) - yz * yz
-    sk = np.fft.fftn(S)
-    psi2 = np.array([kfield(sk, L, c, coef=-1.0) for c in range(3)])
+    sk = _fftn(stored(S, dtype), dtype)
+    psi2 = np.array([kfield(sk, L, c, coef=-1.0, dtype=dtype) for c in range(3)])
     return psi1, psi2
 
 
@@ -91,10 +109,46 @@ def readout(field3, pos, N, L):
     return np.stack([np.sum(wts * f.reshape(-1)[nodes], axis=1) for f in field3], axis=1)
 
 
-def force(pos, N, L, coef):
-    count = paint(pos, N, L)
-    dk = np.fft.fftn(count - 1.)
-    return count, np.array([kfield(dk, L, c, coef=coef) for c in range(3)])
+def force(pos, N, L, coef, dtype=np.float64):
+    """(count, F): count as stored; delta = count - 1 is stored before its transform."""
+    count = stored(paint(pos, N, L), dtype)
+    dk = _fftn(stored(count - 1., dtype), dtype)
+    return count, np.array([kfield(dk, L, c, coef=coef, dtype=dtype) for c in range(3)])
+
+
+# ---- the transform-free stages, one function per entry point.  psi1, psi2, pres, F: (3, N, N, N) stored values ----------------
+def _per_particle(f3):
+    return np.asarray(f3, dtype=np.float64).reshape(3, -1).T
+
+
+def init(psi1, psi2, L, d1, d2):
+    """fb_cola_init: positions (N^3, 3) = wrap((q + d1 Psi1) + d2 Psi2)."""
+    N = np.asarray(psi1).shape[-1]
+    return wrap((lagrangian(N, L) + d1 * _per_particle(psi1)) + d2 * _per_particle(psi2), L)
+
+
+def kick(F, psi1, psi2, pres, pos, L, coef, drift, dtype=np.float64):
+    """fb_cola_kick: (pres (3, N, N, N) as stored, pos)."""
+    N = np.asarray(psi1).shape[-1]
+    cK, dP1, dP2, Dr, dD1, dD2 = [float(c) for c in coef]
+    p1, p2 = _per_particle(psi1), _per_particle(psi2)
+    g = readout(np.asarray(F, dtype=np.float64), pos, N, L)
+    pn = stored(_per_particle(pres) + ((g * cK - dP1 * p1) - dP2 * p2), dtype)
+    if drift:
+        pos = wrap(pos + ((pn * Dr + dD1 * p1) + dD2 * p2), L)
+    return pn.T.reshape(3, N, N, N), pos
+
+
+def velocity(psi1, psi2, pres, P1, P2, fac):
+    """fb_cola_velocity, all three components: (N^3, 3) fp64."""
+    return fac * ((_per_particle(pres) + P1 * _per_particle(psi1)) + P2 * _per_particle(psi2))
+
+
+def grid_velocity(num, count, dtype=np.float64):
+    """fb_cola_grid_velocity: num / count as stored, 0 where count is 0."""
+    num, count = np.asarray(num, dtype=np.float64), np.asarray(count, dtype=np.float64)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        return np.where(count != 0., stored(num / count, dtype), 0.)
 
 
 def run(delta0, L, cosmo, redshift, redshift_init, n_steps, h=None):

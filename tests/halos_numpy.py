@@ -52,8 +52,11 @@ def _axis(u, window, N):
 
 
 def paint(pos, N, L, window="cic", weights=None, compensated=False):
+    """Particles with a position that is not finite are skipped, as fb_paint skips them."""
     pos = np.asarray(pos, dtype=np.float64).reshape(-1, 3)
     w = np.ones(pos.shape[0]) if weights is None else np.asarray(weights, dtype=np.float64)
+    ok = np.all(np.isfinite(pos), axis=1)
+    pos, w = pos[ok], w[ok]
     mesh = np.zeros((N, N, N))
     ax = [_axis(pos[:, a] * (N / L[a]), window, N) for a in range(3)]
     for m0, w0 in ax[0]:
