@@ -75,6 +75,9 @@ SIGNATURES = {
     "fb_bin_power_kmu": (c_int, [c_void_p, c_void_p, c_void_p, P_double, c_int, c_int, c_int, P_double, c_void_p]),
     "fb_power_spectrum_kmu": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, P_double, c_int, c_int, c_int,
                                       P_double, c_void_p]),
+    "fb_bispectrum": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, P_double, c_int, c_int, P_double,
+                              c_void_p]),
+    "fb_device_memory": (c_int, [ctypes.POINTER(c_i64), ctypes.POINTER(c_i64)]),
     "fb_halo_lambda": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_int, c_double, c_double, c_int,
                                c_void_p, c_void_p]),
     "fb_halo_counts": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_double, c_void_p, c_int, c_double, c_double, c_int,

@@ -1008,6 +1008,69 @@ class CosmoBox(object):
             return k, mu, power, modes
         return k[:, 0].copy(), (power[:, 0].copy() if ps is None else power), modes[:, 0].copy()
 
+    # ------------------------------------------------------------ bispectrum in triangle bins
+    def bispectrum(self, delta_x=None, kbins=None, dk=None, kmin=0., kmax=None, reduced=False):
+        """Additive: the bispectrum of a real field in bins of three |k| shells, by the FFT estimator (Scoccimarro 2000;
+        Sefusatti et al. 2016), with the conventions of ``power_spectrum``:
+
+            D = fftn(d) (unnormalised; k = 0 never enters),  k_a = m_a (2 pi / L_a) (m_a the signed FFT index);
+            shell S_b = every mode m != 0 of the full grid with |k| in [e_b, e_b+1);
+            I_b(x) = sum over S_b of D(m) exp(+2 pi i m.x / N),  U_b the same with D = 1;
+            for the shell triples b1 <= b2 <= b3 in itertools.combinations_with_replacement(range(nb), 3) order:
+            ntri = sum_x U_b1 U_b2 U_b3 / N^3, the number of (m1, m2, m3) in S_b1 x S_b2 x S_b3 with m1 + m2 + m3 = 0
+            modulo N on every axis;  B = (V^2 / N^12) sum_x I_b1 I_b2 I_b3 / ntri,  V = Lx Ly Lz;
+            Q = B / (P1 P2 + P2 P3 + P3 P1) with P_b the mean of (V / N^6) |D|^2 over S_b.
+
+        Returns ``(k, B, ntri)``, or ``(k, B, Q, ntri)`` with ``reduced=True``: ``k`` (T, 3) holds the mean |k| of each
+        triple's shells, the others are (T,), T = nb (nb + 1) (nb + 2) / 6; float64, writeable.  Triples without a triangle
+        are NaN in k, B and Q.  Triangles close modulo N, which is what the estimator computes: with the last edge at or below
+        (2/3) pi N / max(L) no triangle closes through an alias.  Edges: ``kbins``; or np.arange(kmin, kmax + dk/2, dk) when
+        ``dk`` is given; by default np.linspace(kmin, kmax, 17) with kmax = (2/3) pi N / max(L) (16 shells); 1 to 32 shells.
+        The shell cubes are held in the box's precision, their products and sums are fp64 in a fixed order (two calls agree bit
+        for bit); ntri is formed in fp64 whatever the precision, once per edge set.  The nb cubes must fit in device memory
+        (8 GiB at 512^3 in single precision with 16 shells): MemoryError before any kernel runs otherwise.  ``delta_x``
+        (default ``self.delta_x``) takes whatever ``power_spectrum`` takes.  The box's state (delta_x, stored spectrum,
+        realisation counter, P(k) bins) is left as it was.  Bad arguments raise ValueError before any device work."""
+        N = self.N
+        L = (self.Lx, self.Ly, self.Lz)
+        edges = hostgeom.bispectrum_edges(L, N, dk=dk, kmin=kmin, kmax=kmax, kbins=kbins)
+        nb = edges.size - 1
+        if N > 1024:
+            raise ValueError("bispectrum: grids up to 1024^3")
+        eng = self.engine
+        need = eng.bispectrum_bytes(nb)
+        if eng.precision != "f64" and edges.tobytes() not in self.__dict__.get("_bk_triangles", {}):
+            need *= 2                                  # the triangle counts of a new edge set: the same cubes in fp64
+        have = eng.free_bytes()
+        if need > have:
+            raise MemoryError("bispectrum: %d shell cubes and their work spectra take %.1f GiB, %.1f GiB are free"
+                              % (nb, need / 2. ** 30, have / 2. ** 30))
+        d1, _ = self._two_fields(delta_x, None)
+        ntri = self._bispectrum_triangles(edges)
+        raw = eng.bispectrum(d1, edges)
+        k, B, Q, ntri = hostgeom.finish_bispectrum(raw, ntri, nb, L, N)
+        return (k, B, Q, ntri) if reduced else (k, B, ntri)
+
+    def _bispectrum_triangles(self, edges):
+        """ntri of an edge set: from the unit spectrum on a double-precision plan of this grid (the box's own, or a twin of
+        a single-precision box), rounded to integers and kept per edge set."""
+        cache = self.__dict__.setdefault("_bk_triangles", {})
+        key = edges.tobytes()
+        if key not in cache:
+            eng = self.engine
+            if eng.precision != "f64":
+                twin = eng.__dict__.get("_f64_twin")
+                if twin is None:
+                    twin = Engine(self.N, (self.Lx, self.Ly, self.Lz), self._axis2, self._ksc, self._kpar, self.z,
+                                  precision="f64", device=eng.device, stream=(eng.stream.value if eng.stream else None))
+                    eng.__dict__["_f64_twin"] = twin
+                eng = twin
+            if len(cache) >= 16:
+                cache.pop(next(iter(cache)))
+            cache[key] = hostgeom.bispectrum_ntri(eng.bispectrum(None, edges, unit=True), edges.size - 1, self.N)
+            eng.release_idle_buffers()
+        return cache[key]
+
     # ------------------------------------------------------------ painting a catalogue
     def paint_catalogue(self, positions, weights=None, window='cic', compensated=False):
         """Additive: mass assignment of a catalogue onto this box's grid, what the reference's examples take from nbodykit as

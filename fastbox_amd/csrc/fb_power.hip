@@ -5,6 +5,7 @@
 #include "fb_plan.h"
 #include "fb_api_util.h"
 #include "fb_field_kernels.h"
+#include "fb_kshell.h"
 #include <algorithm>
 #include <cmath>
 #include <vector>
@@ -231,18 +232,6 @@ int pk_check(const double* kedges, int nk, int nmu, int lmax) {
     for (int q = 0; q < nk; ++q) FB_REQUIRE(std::isfinite(kedges[q]), "k edges must be finite (the last may be inf)");
     for (int q = 1; q <= nk; ++q) FB_REQUIRE(kedges[q] > kedges[q - 1], "k edges must be strictly ascending");
     return FB_OK;
-}
-
-// the least double x >= 0 with sqrt(x) >= e (sqrt correctly rounded, as on the device and in numpy)
-double sq_threshold(double e) {
-    if (e <= 0.0) return 0.0;
-    double x = e * e;
-    while (!(std::sqrt(x) >= e)) x = std::nextafter(x, INFINITY);
-    for (;;) {
-        const double d = std::nextafter(x, 0.0);
-        if (x > 0.0 && std::sqrt(d) >= e) x = d; else break;
-    }
-    return x;
 }
 
 int bin_power_kmu(fb_plan* p, const void* half1, const void* half2, const double* kedges, int nk, int nmu, int lmax,

@@ -717,6 +717,37 @@ class Engine(object):
                   out.ctypes.data_as(_lib.P_double), self.stream)
         return out
 
+    # -- bispectrum in triangle bins -----------------------------------------------------------
+    BK_SPLIT = 4        # shells written per read of the spectrum (FB_BK_SPLIT of the library)
+
+    def bispectrum_bytes(self, nb):
+        """Device bytes fb_bispectrum needs beside the field: nb real cubes, the spectrum and the shells of one batch."""
+        return nb * self.nbytes[REAL] + (1 + min(nb, self.BK_SPLIT)) * self.nbytes[HALF]
+
+    def free_bytes(self):
+        """Bytes a new allocation can draw on: what the driver reports free plus this engine's idle pooled buffers."""
+        free, total = _lib.c_i64(0), _lib.c_i64(0)
+        with _lib.on_device(self.device):
+            _lib.call("fb_device_memory", ctypes.byref(free), ctypes.byref(total))
+        idle = sum(k * len(v) for k, v in self._pool.items() if k != "closed")
+        return free.value + idle
+
+    def bispectrum(self, real, kedges, unit=False):
+        """fb_bispectrum: the record [sum_x I_b1 I_b2 I_b3 per triple; modes, sum |k|, sum |D|^2 per shell] (host, fp64) of a
+        real device field, or with ``unit`` of the spectrum that is 1 on every mode (N^3 times the triangle counts; ``real``
+        is not used).  Work buffers come from the pool; waits for the stream."""
+        kedges = np.ascontiguousarray(kedges, dtype=np.float64)
+        nb = kedges.size - 1
+        out = np.zeros(nb * (nb + 1) * (nb + 2) // 6 + 3 * nb)
+        nwork = min(nb, self.BK_SPLIT)
+        cubes = self._alloc_bytes(nb * self.nbytes[REAL])
+        shells = self._alloc_bytes(nwork * self.nbytes[HALF])
+        wh = None if unit else self.empty(HALF)
+        _lib.call("fb_bispectrum", self._plan, None if unit else real.ptr, None if unit else wh.ptr, shells.ptr, nwork,
+                  cubes.ptr, kedges.ctypes.data_as(_lib.P_double), nb, 1 if unit else 0, out.ctypes.data_as(_lib.P_double),
+                  self.stream)
+        return out
+
     # -- COLA particle mesh -------------------------------------------------------------------
     def cola_buffers(self):
         """The state of one COLA run: pos (fp64 [N^3][3]), psi1, psi2, pres, force ([3][N^3] plan precision) as raw

@@ -340,3 +340,76 @@ def finish_power(raw, nk, nmu, poles=None):
                 sums[l] = raw[lo:lo + nk]
         power = np.array([np.where(e1, np.nan, (2 * l + 1) * sums[l] / m1) for l in poles])
     return k, mu, power, modes
+
+
+# ---- bispectrum in triangle bins (CosmoBox.bispectrum) ---------------------------------------------------------------------
+BK_MAX_SHELLS = 32           # FB_BK_MAX_SHELLS of the library: two 16-row tiles of the contraction
+BK_DEFAULT_SHELLS = 16
+
+
+def bispectrum_edges(L, N, dk=None, kmin=0., kmax=None, kbins=None):
+    """Shell edges in |k|: ``kbins`` as given; with ``dk`` np.arange(kmin, kmax + dk/2, dk); otherwise
+    np.linspace(kmin, kmax, 17) (16 shells).  kmax = (2/3) pi N / max(L_a) by default: below it no triangle closes through
+    an alias.  Strictly ascending, first edge >= 0, all finite but the last, 1 to 32 shells; ValueError otherwise."""
+    if kbins is not None:
+        if dk is not None:
+            raise ValueError("give kbins or dk, not both")
+        edges = np.array(kbins, dtype=np.float64)
+    else:
+        kmax = (2. / 3.) * np.pi * N / float(np.max(L)) if kmax is None else float(kmax)
+        if dk is None:
+            edges = np.linspace(float(kmin), kmax, BK_DEFAULT_SHELLS + 1)
+        else:
+            dk = float(dk)
+            if not dk > 0:
+                raise ValueError("dk must be positive")
+            if not (kmax - float(kmin)) / dk <= 4 * BK_MAX_SHELLS:         # (refused below; never build a huge arange)
+                raise ValueError("k shells: at most %d" % BK_MAX_SHELLS)
+            edges = np.arange(float(kmin), kmax + 0.5 * dk, dk, dtype=np.float64)
+    if edges.ndim != 1 or edges.size < 2 or edges.size > BK_MAX_SHELLS + 1:
+        raise ValueError("k shells: between 2 and %d edges (1 to %d shells), got %r"
+                         % (BK_MAX_SHELLS + 1, BK_MAX_SHELLS, edges.shape))
+    if not np.all(np.isfinite(edges[:-1])) or np.isnan(edges[-1]) or not edges[0] >= 0. or not np.all(np.diff(edges) > 0):
+        raise ValueError("k shell edges must be strictly ascending and start at >= 0")
+    return edges
+
+
+def bispectrum_triples(nb):
+    """(T, 3) shell indices b1 <= b2 <= b3 in itertools.combinations_with_replacement(range(nb), 3) order,
+    T = nb (nb + 1) (nb + 2) / 6."""
+    import itertools
+    if isinstance(nb, bool) or not isinstance(nb, (int, np.integer)) or not 1 <= nb <= BK_MAX_SHELLS:
+        raise ValueError("the number of shells must be an integer in 1..%d, got %r" % (BK_MAX_SHELLS, nb))
+    return np.array(list(itertools.combinations_with_replacement(range(int(nb)), 3)), dtype=np.intp).reshape(-1, 3)
+
+
+def bispectrum_ntri(raw, nb, N):
+    """Closed triangles per triple from the record of a unit-spectrum pass of fb_bispectrum (sum_x U_b1 U_b2 U_b3 = N^3
+    ntri, formed in fp64): rounded to the nearest integer."""
+    T = nb * (nb + 1) * (nb + 2) // 6
+    return np.rint(np.asarray(raw, dtype=np.float64)[:T] / float(N) ** 3)
+
+
+def finish_bispectrum(raw, ntri, nb, L, N):
+    """From fb_bispectrum's record [sum_x I_b1 I_b2 I_b3 (T); modes, sum |k|, sum |D|^2 (nb each)] and the triangle counts:
+    (k (T, 3), B (T,), Q (T,), ntri (T,)) with B = (V^2 / N^12) sum / ntri, k the mean |k| of each triple's shells,
+    Q = B / (P1 P2 + P2 P3 + P3 P1), P_b = (V / N^6) sum |D|^2 / modes.  Triples without a triangle are NaN in k, B and Q;
+    an empty shell has mean |k| NaN."""
+    raw = np.asarray(raw, dtype=np.float64)
+    tri = bispectrum_triples(nb)
+    T = tri.shape[0]
+    sums = raw[:T]
+    modes, sk, sp = (raw[T + q * nb:T + (q + 1) * nb] for q in range(3))
+    ntri = np.array(ntri, dtype=np.float64)
+    n3 = float(N) ** 3
+    V = float(L[0]) * float(L[1]) * float(L[2])
+    with np.errstate(all="ignore"):
+        kbar = np.where(modes == 0, np.nan, sk / modes)
+        P = np.where(modes == 0, np.nan, (V / (n3 * n3)) * sp / modes)
+        empty = ntri == 0
+        B = np.where(empty, np.nan, ((V * V) / n3 ** 4) * sums / ntri)
+        k = kbar[tri]
+        k[empty] = np.nan
+        p1, p2, p3 = P[tri[:, 0]], P[tri[:, 1]], P[tri[:, 2]]
+        Q = B / (p1 * p2 + p2 * p3 + p3 * p1)
+    return k, B, Q, ntri

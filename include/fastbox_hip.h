@@ -236,6 +236,34 @@ int fb_bin_power_kmu(fb_plan* plan, const void* half1, const void* half2, const 
 int fb_power_spectrum_kmu(fb_plan* plan, const void* real1, const void* real2, void* work_half1, void* work_half2,
                           const double* kedges, int nk, int nmu, int lmax, double* out_host, void* stream);
 
+/* ---- bispectrum in triangle bins ----------------------------------------------------------------------------------- */
+/* The FFT estimator of the bispectrum of a real field d (Scoccimarro 2000; Sefusatti et al. 2016) in bins of three |k| shells.
+ * The reference and nbodykit have none: this definition is the contract.  It follows the conventions of fb_bin_power_kmu:
+ *   D = fftn(d) (unnormalised; the mean is not subtracted, k = 0 never enters); k_a = m_a (2 pi / L_a), m_a the signed index
+ *   (Nyquist negative); |k| = sqrt((k_x k_x + k_y k_y) + k_z k_z) in fp64, no contraction;
+ *   shell S_b = {m != 0 of the full grid : np.digitize(|k|, kedges) - 1 == b}, b = 0 .. nb - 1;
+ *   I_b(x) = sum_{m in S_b} D(m) exp(+2 pi i m.x / N) (real: S_b is symmetric under m -> -m mod N); U_b the same with D = 1;
+ *   for every triple t = (b1 <= b2 <= b3), in itertools.combinations_with_replacement(range(nb), 3) order,
+ *     ntri_t = sum_x U_b1 U_b2 U_b3 / N^3 = #{(m1, m2, m3) in S_b1 x S_b2 x S_b3 : m1 + m2 + m3 = 0 (mod N, per axis)},
+ *     B_t = (V^2 / N^12) sum_x I_b1 I_b2 I_b3 / ntri_t,  V = Lx Ly Lz.
+ *   Triangles close modulo N: with kedges[nb] <= (2/3) pi N / max(L) none closes through an alias.  The cubes I_b are held in
+ *   the plan's precision; their products and sums over x are fp64 on the matrix cores, in a fixed order (two calls agree bit
+ *   for bit).
+ * Limits (FB_ERR_INVALID otherwise): kedges[nb + 1] strictly ascending, kedges[0] >= 0, all finite but the last; 1 <= nb <= 32;
+ *   1 <= nwork <= 4; N <= 1024.
+ * fb_bispectrum: fb_fft_r2c of `real` into work_half; then, nwork shells per read of it, the spectrum is split into
+ *   work_shells (nwork half spectra, destroyed) and each shell goes through fb_fft_c2r into its cube of `cubes` (nb real
+ *   fields, which hold the I_b afterwards); one sweep over the voxels then forms every triple's sum.  unit != 0: D = 1 on every
+ *   mode (real and work_half are not used and may be NULL), i.e. the U_b and N^3 ntri_t -- data-independent, so callers keep
+ *   it per edge set, and form it on a double-precision plan.  out_host[T + 3 nb], T = nb (nb + 1) (nb + 2) / 6:
+ *     sum[T] (sum_x I_b1 I_b2 I_b3), then per shell modes[nb] (|S_b|), sum_k[nb] (sum |k|), sum_p[nb] (sum |D|^2); cells of
+ *   the half spectrum with 0 < m_z < N/2 count twice.  P_b = (V / N^6) sum_p / modes is the shell's power, the reduced
+ *   bispectrum Q_t = B_t / (P_b1 P_b2 + P_b2 P_b3 + P_b3 P_b1).  Every grid a plan accepts up to 1024^3.  Synchronises.
+ * fb_device_memory: free and total bytes of the calling thread's current device (hipMemGetInfo). */
+int fb_bispectrum(fb_plan* plan, const void* real, void* work_half, void* work_shells, int nwork, void* cubes,
+                  const double* kedges, int nb, int unit, double* out_host, void* stream);
+int fb_device_memory(int64_t* free_bytes, int64_t* total_bytes);
+
 /* ---- halo tracers (fastbox/halos.py, examples/example_halos.py) --------------------------------------------------- */
 /* fb_halo_lambda: the expected count per voxel, lam_out (DEVICE double[N^3]), exactly halo_count_field's expression
  * (halos.py:92-114) in fp64 whatever the plan's precision:
