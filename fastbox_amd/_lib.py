@@ -100,6 +100,11 @@ SIGNATURES = {
     "fb_merge_regions": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_double, c_void_p, ctypes.POINTER(c_i64), c_void_p]),
     "fb_stack_voids": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_i64, P_double, c_void_p, c_int, c_void_p,
                                c_void_p, c_void_p, c_void_p]),
+    "fb_fof_work_bytes": (c_i64, [c_i64, c_i64]),
+    "fb_fof_link": (c_int, [c_void_p, c_void_p, c_i64, c_double, P_i32, c_void_p, c_i64, c_void_p, P_i32, P_double, c_void_p]),
+    "fb_fof_sizes": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_i64), c_void_p]),
+    "fb_fof_catalogue": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_void_p, c_void_p,
+                                 c_void_p, c_void_p, P_i32, c_void_p]),
     "fb_real_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_void_p]),
     "fb_real_multiply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fb_real_to_complex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),

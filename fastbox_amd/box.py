@@ -1087,6 +1087,15 @@ class CosmoBox(object):
         from . import halos
         return halos.paint(self, positions, weights=weights, window=window, compensated=compensated)
 
+    # ------------------------------------------------------------ friends-of-friends halos
+    def find_halos(self, particles, **kw):
+        """Additive: the friends-of-friends halos of a particle set in this box -- the ``ColaParticles`` of
+        ``realise_density_cola(return_particles=True)``, a HaloCatalogue or a host (n, 3) array -- as a ``FoFHalos``
+        catalogue (centres of mass, counts, masses, mean velocities, per-particle labels), found on the device.  Keywords and
+        definition: ``fastbox_amd.halos.find_halos_fof``; DESIGN.md section 4."""
+        from . import halos
+        return halos.find_halos_fof(self, particles, **kw)
+
     def sigmaR(self, R):
         """RMS of the field smoothed with a top-hat of R Mpc/h, from the binned power
         spectrum (box.py:657-683; scipy's simps is spelled simpson since 1.14)."""

@@ -1,0 +1,569 @@
+// Friends-of-friends halo finding on a particle set (nbodykit's FOF): cell binning, the pair search with a
+// union-find over the particles, the flattening of the forest, group sizes and the catalogue of the groups kept.  Particle data
+// are fp64 whatever the plan's precision; the plan gives the box and the device.  See include/fastbox_hip.h for the entry points.
+//
+// No contraction anywhere in this file: the wrapped positions, the minimum-image differences and d^2 = (dx dx + dy dy) + dz dz
+// must be the doubles of the numpy statement (tests/fof_numpy.py), so that a pair is linked on the device exactly when it is there.
+#pragma clang fp contract(off)
+#include "../../include/fastbox_hip.h"
+#include "fb_plan.h"
+#include "fb_api_util.h"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#define FB_FOF_TILE 64                   // particles per LDS tile = lanes per workgroup of the pair search (FOF_TILE of halos.py)
+#define FB_FOF_SMALL 256                 // bytes at the head of every work buffer: the words below
+#define FB_FOF_MAX_JUMPS 40              // pointer-jumping rounds of the flattening (path lengths halve: 2^31 particles need 32)
+#define FB_FOF_ERR_POS 1u                // error word: a position that is not finite, or too large to wrap into the box
+#define FB_FOF_ERR_LOOP 2u               //             a find or union loop hit its cap
+#define FB_FOF_ERR_VEL 4u                //             a velocity that is not finite
+#define FB_FOF_NONE 0xFFFFFFFFu
+#define FB_FOF_WRAP_MAX 4503599627370496.0   // 2^52: positions must satisfy |x| < 2^52 L
+#define FB_FOF_SCAN_PER 16
+#define FB_FOF_SCAN_CH (256 * FB_FOF_SCAN_PER)
+
+namespace {
+
+// words of the small block: u32 [0] error, [1] changed, [2] items / kept; u64 [2] groups; double [3] max |v|
+struct FofSmall { unsigned err, changed, count, pad; unsigned long long groups; unsigned long long vmax_bits; };
+
+struct FofGeom { double L[3]; double s[3]; int nc[3]; };        // box, cells per unit length, cells per axis
+
+__device__ __forceinline__ double fof_wrap(double x, double L) {
+    x = x - L * floor(x / L);
+    if (x < 0.0) x += L;
+    if (x >= L) x -= L;
+    return x;
+}
+__device__ __forceinline__ double fof_min_image(double d, double L) {
+    const double h = 0.5 * L;
+    if (d > h) d -= L;
+    else if (d < -h) d += L;
+    return d;
+}
+__device__ __forceinline__ unsigned fof_cell(const FofGeom& g, double w0, double w1, double w2) {
+    const int c0 = max(min((int)(w0 * g.s[0]), g.nc[0] - 1), 0), c1 = max(min((int)(w1 * g.s[1]), g.nc[1] - 1), 0),
+              c2 = max(min((int)(w2 * g.s[2]), g.nc[2] - 1), 0);
+    return ((unsigned)c0 * (unsigned)g.nc[1] + (unsigned)c1) * (unsigned)g.nc[2] + (unsigned)c2;
+}
+
+// ---- 1. cell binning ----------------------------------------------------------------------------------------------------
+// the cell of every particle and the cells' occupancy (integer adds: any order).  A position that is not finite, that has
+// |x| >= 2^52 L (floor(x / L) is no longer the integer it stands for, the wrap is meaningless), or whose wrapped value
+// does not land in [0, L) all the same, sets the error word and enters no cell
+__global__ __launch_bounds__(256) void k_fof_bin(const double* pos, unsigned long long n, FofGeom g, unsigned* cellid, unsigned* hist,
+                                                 unsigned* err) {
+    bool bad = false;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
+        const double x0 = pos[3 * i], x1 = pos[3 * i + 1], x2 = pos[3 * i + 2];
+        const double w0 = fof_wrap(x0, g.L[0]), w1 = fof_wrap(x1, g.L[1]), w2 = fof_wrap(x2, g.L[2]);
+        const bool small = fabs(x0) < FB_FOF_WRAP_MAX * g.L[0] && fabs(x1) < FB_FOF_WRAP_MAX * g.L[1] && fabs(x2) < FB_FOF_WRAP_MAX * g.L[2];
+        if (!(small && w0 >= 0.0 && w0 < g.L[0] && w1 >= 0.0 && w1 < g.L[1] && w2 >= 0.0 && w2 < g.L[2])) {     // NaN fails every test
+            bad = true; cellid[i] = FB_FOF_NONE; continue;
+        }
+        const unsigned c = fof_cell(g, w0, w1, w2);
+        cellid[i] = c;
+        atomicAdd(&hist[c], 1u);
+    }
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(err, FB_FOF_ERR_POS);
+}
+
+// exclusive scan of in[0..M) into out[0..M], out[M] = the total, in three steps (after the scan of fb_halo.hip): chunk sums, a
+// scan of the chunk sums in one workgroup, the chunks themselves.  The total stays below 2^32: it is the number of particles.
+__device__ __forceinline__ unsigned scan_in(const unsigned* in, unsigned long long j, unsigned long long M) { return j < M ? in[j] : 0u; }
+__global__ __launch_bounds__(256) void k_fof_scan_chunks(const unsigned* in, unsigned long long M, unsigned* csum) {
+    const unsigned long long j0 = (unsigned long long)blockIdx.x * FB_FOF_SCAN_CH;
+    unsigned s = 0;
+    for (int q = 0; q < FB_FOF_SCAN_PER; ++q) s += scan_in(in, j0 + (unsigned long long)q * 256 + threadIdx.x, M);
+    __shared__ unsigned tot;
+    if (threadIdx.x == 0) tot = 0;
+    __syncthreads();
+    atomicAdd(&tot, s);
+    __syncthreads();
+    if (threadIdx.x == 0) csum[blockIdx.x] = tot;
+}
+__device__ unsigned block_exscan(unsigned v, unsigned* total) {
+    __shared__ unsigned sh[256];
+    sh[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {
+        const unsigned a = threadIdx.x >= (unsigned)o ? sh[threadIdx.x - o] : 0u;
+        __syncthreads();
+        sh[threadIdx.x] += a;
+        __syncthreads();
+    }
+    const unsigned incl = sh[threadIdx.x];
+    *total = sh[255];
+    __syncthreads();
+    return incl - v;
+}
+__global__ __launch_bounds__(256) void k_fof_scan_top(unsigned* csum, int nc) {
+    unsigned carry = 0;
+    for (int base = 0; base < nc; base += 256) {
+        const int i = base + threadIdx.x;
+        const unsigned v = i < nc ? csum[i] : 0u;
+        unsigned tot;
+        const unsigned ex = block_exscan(v, &tot);
+        if (i < nc) csum[i] = carry + ex;
+        carry += tot;
+    }
+}
+__global__ __launch_bounds__(256) void k_fof_scan_apply(const unsigned* in, unsigned long long M, const unsigned* csum, unsigned* out) {
+    const unsigned long long j0 = (unsigned long long)blockIdx.x * FB_FOF_SCAN_CH + (unsigned long long)threadIdx.x * FB_FOF_SCAN_PER;
+    unsigned w[FB_FOF_SCAN_PER], s = 0;
+    for (int q = 0; q < FB_FOF_SCAN_PER; ++q) { w[q] = scan_in(in, j0 + q, M); s += w[q]; }
+    unsigned tot;
+    unsigned run = csum[blockIdx.x] + block_exscan(s, &tot);
+    for (int q = 0; q < FB_FOF_SCAN_PER; ++q) {
+        if (j0 + q <= M) out[j0 + q] = run;
+        run += w[q];
+    }
+}
+
+// the permutation by cell and the wrapped positions in that order; every particle becomes its own root.  The order inside a
+// cell is that of the atomic cursor: arbitrary, and no output depends on it.
+__global__ __launch_bounds__(256) void k_fof_scatter(const double* pos, unsigned long long n, FofGeom g, const unsigned* cellid,
+                                                     const unsigned* start, unsigned* cursor, unsigned* perm, double* spos,
+                                                     unsigned* par) {
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
+        const unsigned c = cellid[i];
+        const unsigned long long slot = (unsigned long long)start[c] + atomicAdd(&cursor[c], 1u);
+        perm[slot] = (unsigned)i;
+        spos[3 * slot] = fof_wrap(pos[3 * i], g.L[0]);
+        spos[3 * slot + 1] = fof_wrap(pos[3 * i + 1], g.L[1]);
+        spos[3 * slot + 2] = fof_wrap(pos[3 * i + 2], g.L[2]);
+        par[i] = (unsigned)i;
+    }
+}
+
+// the tiles k >= 1 of the cells that hold more than one tile, as (cell, k) pairs in arbitrary order: at most n / TILE of them
+__global__ __launch_bounds__(256) void k_fof_items(const unsigned* start, unsigned long long ncells, unsigned* items, unsigned* nitems) {
+    for (unsigned long long c = (unsigned long long)blockIdx.x * 256 + threadIdx.x; c < ncells; c += (unsigned long long)gridDim.x * 256) {
+        const unsigned cnt = start[c + 1] - start[c];
+        for (unsigned k = 1; k * FB_FOF_TILE < cnt; ++k) {
+            const unsigned slot = atomicAdd(nitems, 1u);
+            items[2ull * slot] = (unsigned)c;
+            items[2ull * slot + 1] = k;
+        }
+    }
+}
+
+// ---- 2. pair search and union ---------------------------------------------------------------------------------------------
+// Union-find over par[]: par[i] <= i always (the larger root is hooked under the smaller), so the forest has no cycle and the
+// root of a finished group is its least member.  Every access to par in this kernel is a relaxed agent-scope atomic: the
+// compiler cannot keep a word in a register, and no load is served by a CU's own L1.  A word that is older than the newest
+// one is still an ancestor (the argument above k_ws_jump of fb_voids.hip): only a successful compare-and-swap on a true root
+// changes the forest, path halving writes ancestors into non-roots only, and a node that stops being a root never becomes
+// one again -- so a stale read costs steps, never a wrong link.
+__device__ __forceinline__ unsigned par_load(const unsigned* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void par_store(unsigned* p, unsigned v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+// the root of x as far as this lane can see, with path halving; FB_FOF_NONE (and the error word) past the cap.  Every word
+// ever stored in par[i] is <= i, so each step that does not return moves x to a strictly smaller index (g <= p < x): a find
+// takes at most n steps, and cap = n + 1 is reached only if the forest is corrupt.
+__device__ unsigned fof_find(unsigned* par, unsigned x, unsigned cap, unsigned* err) {
+    for (unsigned it = 0; it < cap; ++it) {
+        const unsigned p = par_load(par + x);
+        if (p == x) return x;
+        const unsigned g = par_load(par + p);
+        if (g != p) par_store(par + x, g);
+        x = g;
+    }
+    atomicOr(err, FB_FOF_ERR_LOOP);
+    return FB_FOF_NONE;
+}
+// join the groups of a and b: hook the larger root under the smaller by compare-and-swap on the larger root's own word.  A
+// failure means that root was hooked elsewhere in between: go on from the parent the swap returned (a true one, not a cached
+// one).  That parent and `small` are both below `big`, so the larger root of the next attempt is strictly smaller: at most n
+// attempts, the same cap.
+__device__ void fof_union(unsigned* par, unsigned a, unsigned b, unsigned cap, unsigned* err) {
+    for (unsigned it = 0; it < cap; ++it) {
+        a = fof_find(par, a, cap, err);
+        b = fof_find(par, b, cap, err);
+        if (a == FB_FOF_NONE || b == FB_FOF_NONE || a == b) return;
+        const unsigned big = a > b ? a : b, small = a > b ? b : a;
+        const unsigned old = atomicCAS(par + big, big, small);
+        if (old == big) return;
+        a = small; b = old;
+    }
+    atomicOr(err, FB_FOF_ERR_LOOP);
+}
+
+// One workgroup of one wave per (cell, home tile): the home tile and, tile by tile, the particles of the cell itself and of its
+// neighbour cells go through LDS; the TILE x TILE pairs are spread over the lanes.  Every pair is decided by its own
+// minimum-image d^2, not by a shift per cell, so a neighbour cell met twice (fewer than 3 cells along an axis: +1 and -1 are the
+// same cell) only repeats unions that are already done.  half != 0 (3 or more cells on every axis): the cell itself and the 13
+// neighbours of the upper half shell, each adjacent pair of cells once; else all 27 offsets.  Inside one cell a pair is taken
+// once, by its slots.  items NULL: work item w is tile 0 of cell w; else the (cell, tile) pair items[2 w], items[2 w + 1].
+__global__ __launch_bounds__(FB_FOF_TILE) void k_fof_link(FofGeom g, const unsigned* start, const unsigned* perm, const double* spos,
+                                                          unsigned* par, double ell2, const unsigned* items, unsigned long long total,
+                                                          int half, unsigned cap, unsigned* err) {
+    __shared__ double hx[FB_FOF_TILE], hy[FB_FOF_TILE], hz[FB_FOF_TILE], nx[FB_FOF_TILE], ny[FB_FOF_TILE], nz[FB_FOF_TILE];
+    __shared__ unsigned hid[FB_FOF_TILE], nid[FB_FOF_TILE];
+    const int t = threadIdx.x;
+    for (unsigned long long w = blockIdx.x; w < total; w += gridDim.x) {
+        const unsigned c = items ? items[2 * w] : (unsigned)w, k = items ? items[2 * w + 1] : 0u;
+        const unsigned b0 = start[c], b1 = start[c + 1];
+        if (b1 - b0 <= k * FB_FOF_TILE) continue;                     // an empty cell: the whole workgroup skips it
+        const unsigned h0 = b0 + k * FB_FOF_TILE;
+        const int nh = (int)min(b1 - h0, (unsigned)FB_FOF_TILE);
+        __syncthreads();
+        if (t < nh) {
+            hx[t] = spos[3ull * (h0 + t)]; hy[t] = spos[3ull * (h0 + t) + 1]; hz[t] = spos[3ull * (h0 + t) + 2];
+            hid[t] = perm[h0 + t];
+        }
+        const int c2 = (int)(c % (unsigned)g.nc[2]), c1 = (int)((c / (unsigned)g.nc[2]) % (unsigned)g.nc[1]),
+                  c0 = (int)(c / ((unsigned)g.nc[2] * (unsigned)g.nc[1]));
+        for (int o = half ? 13 : 0; o < 27; ++o) {
+            const int m0 = (c0 + o / 9 - 1 + g.nc[0]) % g.nc[0], m1 = (c1 + (o / 3) % 3 - 1 + g.nc[1]) % g.nc[1],
+                      m2 = (c2 + o % 3 - 1 + g.nc[2]) % g.nc[2];
+            const unsigned m = ((unsigned)m0 * (unsigned)g.nc[1] + (unsigned)m1) * (unsigned)g.nc[2] + (unsigned)m2;
+            const bool same = m == c;
+            const unsigned e0 = start[m], e1 = start[m + 1];
+            for (unsigned q0 = e0; q0 < e1; q0 += FB_FOF_TILE) {
+                const int nn = (int)min(e1 - q0, (unsigned)FB_FOF_TILE);
+                __syncthreads();
+                if (t < nn) {
+                    nx[t] = spos[3ull * (q0 + t)]; ny[t] = spos[3ull * (q0 + t) + 1]; nz[t] = spos[3ull * (q0 + t) + 2];
+                    nid[t] = perm[q0 + t];
+                }
+                __syncthreads();
+                const int np = nh * nn;
+                for (int q = t; q < np; q += FB_FOF_TILE) {
+                    const int i = q / nn, j = q - i * nn;
+                    if (same && h0 + (unsigned)i >= q0 + (unsigned)j) continue;
+                    const double dx = fof_min_image(hx[i] - nx[j], g.L[0]), dy = fof_min_image(hy[i] - ny[j], g.L[1]),
+                                 dz = fof_min_image(hz[i] - nz[j], g.L[2]);
+                    const double d2 = (dx * dx + dy * dy) + dz * dz;
+                    if (d2 < ell2) fof_union(par, hid[i], nid[j], cap, err);
+                }
+            }
+        }
+    }
+}
+
+// ---- 3. flatten -----------------------------------------------------------------------------------------------------------
+// one round of pointer jumping between launches, par[i] = par[par[i]]; *changed |= 1 if some pointer moved (k_ws_jump)
+__global__ __launch_bounds__(256) void k_fof_jump(unsigned* par, unsigned long long n, unsigned* changed) {
+    bool ch = false;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
+        const unsigned v = par[i];
+        const unsigned w = par[v];
+        if (w != v) { par[i] = w; ch = true; }
+    }
+    if (__any(ch) && (threadIdx.x & 63) == 0) atomicOr(changed, 1u);
+}
+
+// ---- 4. sizes and catalogue ---------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_fof_count(const unsigned* root, unsigned long long n, unsigned* count) {
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256)
+        atomicAdd(&count[root[i]], 1u);
+}
+// the number of roots, and the (root, count) pairs of the groups of nmin members or more, in arbitrary order
+__global__ __launch_bounds__(256) void k_fof_tally(const unsigned* root, const unsigned* count, unsigned long long n, unsigned nmin,
+                                                   unsigned* kept, unsigned* nkept, unsigned long long* groups) {
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
+        if (root[i] != (unsigned)i) continue;
+        atomicAdd(groups, 1ull);
+        if (count[i] >= nmin) {
+            const unsigned slot = atomicAdd(nkept, 1u);
+            kept[2ull * slot] = (unsigned)i;
+            kept[2ull * slot + 1] = count[i];
+        }
+    }
+}
+
+__global__ __launch_bounds__(256) void k_fof_rank(const unsigned* sroot, unsigned nk, int* labels) {
+    const unsigned r = blockIdx.x * 256 + threadIdx.x;
+    if (r < nk) labels[sroot[r]] = (int)r;
+}
+// labels holds -1 everywhere but on the roots of the groups kept (k_fof_rank); the members copy their root's word
+__global__ __launch_bounds__(256) void k_fof_label(const unsigned* root, unsigned long long n, int* labels) {
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
+        const unsigned r = root[i];
+        if (r != (unsigned)i) labels[i] = labels[r];
+    }
+}
+// max |v| over all components (the bit pattern of a non-negative double orders as an integer)
+__global__ __launch_bounds__(256) void k_fof_vmax(const double* vel, unsigned long long n3, unsigned long long* vmax_bits, unsigned* err) {
+    double m = 0.0;
+    bool bad = false;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n3; i += (unsigned long long)gridDim.x * 256) {
+        const double a = fabs(vel[i]);
+        if (!(a < INFINITY)) bad = true; else m = fmax(m, a);
+    }
+    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
+    if ((threadIdx.x & 63) == 0) atomicMax(vmax_bits, (unsigned long long)__double_as_longlong(m));
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(err, FB_FOF_ERR_VEL);
+}
+// Fixed point, as k_paint of fb_halo.hip on double-precision plans: a contribution x is added as the integer round(x 2^F) split
+// into hi = floor(x 2^(F - 32)) and lo = x 2^F - hi 2^32 in [0, 2^32], two 64-bit accumulators -- integer adds, so the sums do
+// not depend on the order of the particles.  F = 93 - e with (number of particles) (bound of |x|) < 2^e: hi stays below 2^61.
+__device__ __forceinline__ int fof_exponent(double bound) {
+    int e = 0;
+    if (bound > 0.0) (void)frexp(bound, &e);
+    return 93 - e;
+}
+__device__ __forceinline__ void fof_add(unsigned long long* acc, double x, int F) {
+    const double v = ldexp(x, F);
+    const double hi = floor(v * 2.3283064365386963e-10);
+    const double lo = v - hi * 4294967296.0;
+    atomicAdd(acc, (unsigned long long)(long long)hi);
+    atomicAdd(acc + 1, (unsigned long long)__double2ll_rn(lo));
+}
+__device__ __forceinline__ double fof_sum(const unsigned long long* acc, int F) {
+    return ldexp((double)(long long)acc[0] * 4294967296.0 + (double)acc[1], -F);
+}
+// acc[g][6][2]: per group kept, the sums of the minimum-image offsets from the root's wrapped position and of the velocities
+__global__ __launch_bounds__(256) void k_fof_accum(const double* pos, const double* vel, const unsigned* root, const int* labels,
+                                                   unsigned long long n, FofGeom g, int Fp, const unsigned long long* vmax_bits,
+                                                   unsigned long long* acc) {
+    const int Fv = vel ? fof_exponent((double)n * __longlong_as_double((long long)vmax_bits[0])) : 0;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
+        const int lab = labels[i];
+        if (lab < 0) continue;
+        const unsigned long long r = root[i];
+        unsigned long long* a = acc + 12ull * (unsigned)lab;
+        for (int c = 0; c < 3; ++c) {
+            const double d = fof_min_image(fof_wrap(pos[3 * i + c], g.L[c]) - fof_wrap(pos[3 * r + c], g.L[c]), g.L[c]);
+            fof_add(a + 2 * c, d, Fp);
+            if (vel) fof_add(a + 6 + 2 * c, vel[3 * i + c], Fv);
+        }
+    }
+}
+__global__ __launch_bounds__(256) void k_fof_finish(const double* pos, const unsigned* sroot, const unsigned* scount, unsigned nk,
+                                                    FofGeom g, int Fp, const unsigned long long* vmax_bits, unsigned long long n,
+                                                    const unsigned long long* acc, double* com, double* vmean) {
+    const unsigned r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= nk) return;
+    const int Fv = vmean ? fof_exponent((double)n * __longlong_as_double((long long)vmax_bits[0])) : 0;
+    const double m = (double)scount[r];
+    const unsigned long long i = sroot[r];
+    for (int c = 0; c < 3; ++c) {
+        const double a = fof_wrap(pos[3 * i + c], g.L[c]);
+        com[3ull * r + c] = fof_wrap(a + fof_sum(acc + 12ull * r + 2 * c, Fp) / m, g.L[c]);
+        if (vmean) vmean[3ull * r + c] = fof_sum(acc + 12ull * r + 6 + 2 * c, Fv) / m;
+    }
+}
+
+// ---- host -------------------------------------------------------------------------------------------------------------------
+int grid_for(unsigned long long n, const fb_plan* p) {
+    const unsigned long long b = (n + 255) / 256, cap = 8ull * p->num_cu * 8;
+    return (int)std::max(1ull, std::min(b, cap));
+}
+unsigned long long scan_chunks(unsigned long long m) { return (m + FB_FOF_SCAN_CH - 1) / FB_FOF_SCAN_CH; }
+size_t align16(size_t b) { return (b + 15) / 16 * 16; }
+
+// the work buffer of fb_fof_link: small | spos f64[3 n] | start u32[ncells + 1] | cursor u32[ncells] | csum u32[chunks] |
+// cellid u32[n] | perm u32[n] | items u32[2 (n / TILE + 1)]
+struct FofWork { size_t spos, start, cursor, csum, cellid, perm, items, total; };
+FofWork work_layout(unsigned long long n, unsigned long long ncells) {
+    FofWork w;
+    size_t o = FB_FOF_SMALL;
+    w.spos = o; o += align16((size_t)n * 24);
+    w.start = o; o += align16((size_t)(ncells + 1) * 4);
+    w.cursor = o; o += align16((size_t)ncells * 4);
+    w.csum = o; o += align16((size_t)scan_chunks(ncells + 1) * 4);
+    w.cellid = o; o += align16((size_t)n * 4);
+    w.perm = o; o += align16((size_t)n * 4);
+    w.items = o; o += align16((size_t)(n / FB_FOF_TILE + 1) * 8);
+    w.total = o;
+    return w;
+}
+FofGeom geom_of(const fb_plan* p, const int* nc) {
+    FofGeom g;
+    for (int a = 0; a < 3; ++a) { g.L[a] = p->L[a]; g.nc[a] = nc ? nc[a] : 1; g.s[a] = (double)g.nc[a] / p->L[a]; }
+    return g;
+}
+int read_small(const void* work, FofSmall* h, hipStream_t s) {
+    FB_HIP(hipMemcpyAsync(h, work, sizeof(FofSmall), hipMemcpyDeviceToHost, s));
+    FB_HIP(hipStreamSynchronize(s));
+    return FB_OK;
+}
+int loop_error() {
+    fb_set_error("friends-of-friends: a find or union loop hit its iteration cap");
+    return FB_ERR_STATE;
+}
+
+}  // namespace
+
+extern "C" {
+
+int64_t fb_fof_work_bytes(int64_t n, int64_t ncells) {
+    if (n < 0 || ncells < 1) return -1;
+    return (int64_t)work_layout((unsigned long long)n, (unsigned long long)ncells).total;
+}
+
+int fb_fof_link(fb_plan* p, const double* pos, int64_t n, double link, const int* ncell, void* work, int64_t work_bytes,
+                uint32_t* root_out, int* bad, double* stage_ms, void* stream) {
+    FB_REQUIRE(p && ncell && bad, "null pointer");
+    FB_REQUIRE(n >= 0 && n <= 2147483646ll, "friends-of-friends: 0 <= n <= 2^31 - 2");
+    const double lmin = std::min(p->L[0], std::min(p->L[1], p->L[2]));
+    FB_REQUIRE(link > 0.0 && link < 0.5 * lmin, "friends-of-friends: 0 < linking length < min(L) / 2");
+    unsigned long long ncells = 1;
+    for (int a = 0; a < 3; ++a) {
+        FB_REQUIRE(ncell[a] >= 1 && p->L[a] / (double)ncell[a] >= link, "friends-of-friends: cells of side >= the linking length");
+        ncells *= (unsigned long long)ncell[a];
+        FB_REQUIRE(ncells <= (1ull << 31), "friends-of-friends: at most 2^31 cells");
+    }
+    *bad = 0;
+    if (stage_ms) stage_ms[0] = stage_ms[1] = stage_ms[2] = stage_ms[3] = 0.0;
+    if (n == 0) return FB_OK;
+    FB_REQUIRE(pos && work && root_out, "null pointer");
+    const FofWork w = work_layout((unsigned long long)n, ncells);
+    FB_REQUIRE(work_bytes >= (int64_t)w.total, "friends-of-friends: work buffer smaller than fb_fof_work_bytes");
+    FB_USE_DEVICE(p);
+    hipStream_t s = (hipStream_t)stream;
+    char* wb = (char*)work;
+    FofSmall* sm = (FofSmall*)wb;
+    double* spos = (double*)(wb + w.spos);
+    unsigned *start = (unsigned*)(wb + w.start), *cursor = (unsigned*)(wb + w.cursor), *csum = (unsigned*)(wb + w.csum),
+             *cellid = (unsigned*)(wb + w.cellid), *perm = (unsigned*)(wb + w.perm), *items = (unsigned*)(wb + w.items);
+    const FofGeom g = geom_of(p, ncell);
+    const unsigned long long un = (unsigned long long)n;
+    hipEvent_t ev[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (stage_ms) for (int q = 0; q < 5; ++q) FB_HIP(hipEventCreate(&ev[q]));
+    struct EvGuard { hipEvent_t* e; ~EvGuard() { for (int q = 0; q < 5; ++q) if (e[q]) (void)hipEventDestroy(e[q]); } } evg{ev};
+    if (stage_ms) FB_HIP(hipEventRecord(ev[0], s));
+    // 1. bin
+    FB_HIP(hipMemsetAsync(sm, 0, FB_FOF_SMALL, s));
+    FB_HIP(hipMemsetAsync(cursor, 0, (size_t)ncells * 4, s));
+    hipLaunchKernelGGL(k_fof_bin, dim3(grid_for(un, p)), dim3(256), 0, s, pos, un, g, cellid, cursor, &sm->err);
+    FB_LAUNCH_CHECK("k_fof_bin");
+    FofSmall h;
+    int r = read_small(sm, &h, s);
+    if (r) return r;
+    if (h.err & FB_FOF_ERR_POS) { *bad = 1; return FB_OK; }          // before any linking
+    const int nch = (int)scan_chunks(ncells + 1);
+    hipLaunchKernelGGL(k_fof_scan_chunks, dim3(nch), dim3(256), 0, s, (const unsigned*)cursor, ncells, csum);
+    FB_LAUNCH_CHECK("k_fof_scan_chunks");
+    hipLaunchKernelGGL(k_fof_scan_top, dim3(1), dim3(256), 0, s, csum, nch);
+    FB_LAUNCH_CHECK("k_fof_scan_top");
+    hipLaunchKernelGGL(k_fof_scan_apply, dim3(nch), dim3(256), 0, s, (const unsigned*)cursor, ncells, (const unsigned*)csum, start);
+    FB_LAUNCH_CHECK("k_fof_scan_apply");
+    FB_HIP(hipMemsetAsync(cursor, 0, (size_t)ncells * 4, s));
+    hipLaunchKernelGGL(k_fof_scatter, dim3(grid_for(un, p)), dim3(256), 0, s, pos, un, g, (const unsigned*)cellid, (const unsigned*)start,
+                       cursor, perm, spos, (unsigned*)root_out);
+    FB_LAUNCH_CHECK("k_fof_scatter");
+    hipLaunchKernelGGL(k_fof_items, dim3(grid_for(ncells, p)), dim3(256), 0, s, (const unsigned*)start, ncells, items, &sm->count);
+    FB_LAUNCH_CHECK("k_fof_items");
+    if (stage_ms) FB_HIP(hipEventRecord(ev[1], s));
+    r = read_small(sm, &h, s);
+    if (r) return r;
+    const unsigned long long nitems = h.count;
+    // 2. link: tile 0 of every cell, then the further tiles of the crowded cells
+    const int half = ncell[0] >= 3 && ncell[1] >= 3 && ncell[2] >= 3;
+    const unsigned long long wgmax = 256ull * (unsigned long long)p->num_cu;
+    hipLaunchKernelGGL(k_fof_link, dim3((unsigned)std::min(ncells, wgmax)), dim3(FB_FOF_TILE), 0, s, g, (const unsigned*)start,
+                       (const unsigned*)perm, (const double*)spos, (unsigned*)root_out, link * link, (const unsigned*)nullptr, ncells,
+                       half, (unsigned)n + 1u, &sm->err);
+    FB_LAUNCH_CHECK("k_fof_link");
+    if (stage_ms) FB_HIP(hipEventRecord(ev[2], s));
+    if (nitems) {
+        hipLaunchKernelGGL(k_fof_link, dim3((unsigned)std::min(nitems, wgmax)), dim3(FB_FOF_TILE), 0, s, g, (const unsigned*)start,
+                           (const unsigned*)perm, (const double*)spos, (unsigned*)root_out, link * link, (const unsigned*)items,
+                           nitems, half, (unsigned)n + 1u, &sm->err);
+        FB_LAUNCH_CHECK("k_fof_link");
+    }
+    if (stage_ms) FB_HIP(hipEventRecord(ev[3], s));
+    // 3. flatten
+    for (int round = 0;; ++round) {
+        if (round == FB_FOF_MAX_JUMPS) {
+            fb_set_error("friends-of-friends: pointer jumping did not converge");
+            return FB_ERR_STATE;
+        }
+        FB_HIP(hipMemsetAsync(&sm->changed, 0, sizeof(unsigned), s));
+        hipLaunchKernelGGL(k_fof_jump, dim3(grid_for(un, p)), dim3(256), 0, s, (unsigned*)root_out, un, &sm->changed);
+        FB_LAUNCH_CHECK("k_fof_jump");
+        r = read_small(sm, &h, s);
+        if (r) return r;
+        if (h.err & FB_FOF_ERR_LOOP) return loop_error();
+        if (!h.changed) break;
+    }
+    if (stage_ms) {
+        FB_HIP(hipEventRecord(ev[4], s));
+        FB_HIP(hipEventSynchronize(ev[4]));
+        for (int q = 0; q < 4; ++q) {
+            float ms = 0.f;
+            FB_HIP(hipEventElapsedTime(&ms, ev[q], ev[q + 1]));
+            stage_ms[q] = (double)ms;
+        }
+    }
+    return FB_OK;
+}
+
+int fb_fof_sizes(fb_plan* p, const uint32_t* root, int64_t n, int64_t nmin, void* work, uint32_t* count_out, uint32_t* kept_out,
+                 int64_t* out_host, void* stream) {
+    FB_REQUIRE(p && out_host, "null pointer");
+    FB_REQUIRE(n >= 0 && n <= 2147483646ll && nmin >= 1, "friends-of-friends: 0 <= n <= 2^31 - 2, nmin >= 1");
+    out_host[0] = out_host[1] = 0;
+    if (n == 0) return FB_OK;
+    FB_REQUIRE(root && work && count_out && (kept_out || nmin > n), "null pointer");
+    FB_USE_DEVICE(p);
+    hipStream_t s = (hipStream_t)stream;
+    FofSmall* sm = (FofSmall*)work;
+    const unsigned long long un = (unsigned long long)n;
+    FB_HIP(hipMemsetAsync(sm, 0, FB_FOF_SMALL, s));
+    FB_HIP(hipMemsetAsync(count_out, 0, (size_t)n * 4, s));
+    hipLaunchKernelGGL(k_fof_count, dim3(grid_for(un, p)), dim3(256), 0, s, (const unsigned*)root, un, (unsigned*)count_out);
+    FB_LAUNCH_CHECK("k_fof_count");
+    hipLaunchKernelGGL(k_fof_tally, dim3(grid_for(un, p)), dim3(256), 0, s, (const unsigned*)root, (const unsigned*)count_out, un,
+                       (unsigned)std::min<int64_t>(nmin, 0xFFFFFFFFll), (unsigned*)kept_out, &sm->count, &sm->groups);
+    FB_LAUNCH_CHECK("k_fof_tally");
+    FofSmall h;
+    const int r = read_small(sm, &h, s);
+    if (r) return r;
+    out_host[0] = (int64_t)h.groups;
+    out_host[1] = (int64_t)h.count;
+    return FB_OK;
+}
+
+int fb_fof_catalogue(fb_plan* p, const double* pos, const double* vel, const uint32_t* root, int64_t n, const uint32_t* sorted_roots,
+                     const uint32_t* sorted_counts, int64_t n_kept, void* work, int32_t* labels_out, double* pos_out, double* vel_out,
+                     int* bad, void* stream) {
+    FB_REQUIRE(p && bad, "null pointer");
+    FB_REQUIRE(n >= 0 && n <= 2147483646ll && n_kept >= 0 && n_kept <= n, "friends-of-friends: 0 <= n_kept <= n <= 2^31 - 2");
+    *bad = 0;
+    if (n == 0) return FB_OK;
+    FB_REQUIRE(pos && root && labels_out, "null pointer");
+    FB_REQUIRE(n_kept == 0 || (sorted_roots && sorted_counts && work && pos_out && (vel_out || !vel)), "null pointer");
+    FB_USE_DEVICE(p);
+    hipStream_t s = (hipStream_t)stream;
+    const unsigned long long un = (unsigned long long)n;
+    FB_HIP(hipMemsetAsync(labels_out, 0xFF, (size_t)n * 4, s));
+    if (n_kept == 0) return FB_OK;
+    const unsigned nk = (unsigned)n_kept;
+    FofSmall* sm = (FofSmall*)work;
+    unsigned long long* acc = (unsigned long long*)((char*)work + FB_FOF_SMALL);
+    const FofGeom g = geom_of(p, nullptr);
+    FB_HIP(hipMemsetAsync(work, 0, FB_FOF_SMALL + (size_t)nk * 96, s));
+    hipLaunchKernelGGL(k_fof_rank, dim3((nk + 255) / 256), dim3(256), 0, s, (const unsigned*)sorted_roots, nk, (int*)labels_out);
+    FB_LAUNCH_CHECK("k_fof_rank");
+    hipLaunchKernelGGL(k_fof_label, dim3(grid_for(un, p)), dim3(256), 0, s, (const unsigned*)root, un, (int*)labels_out);
+    FB_LAUNCH_CHECK("k_fof_label");
+    if (vel) {
+        hipLaunchKernelGGL(k_fof_vmax, dim3(grid_for(3 * un, p)), dim3(256), 0, s, vel, 3 * un, &sm->vmax_bits, &sm->err);
+        FB_LAUNCH_CHECK("k_fof_vmax");
+        FofSmall h;
+        const int r = read_small(sm, &h, s);
+        if (r) return r;
+        double vmax;
+        memcpy(&vmax, &h.vmax_bits, sizeof(vmax));
+        if ((h.err & FB_FOF_ERR_VEL) || !std::isfinite((double)n * vmax)) { *bad = 4; return FB_OK; }     // the sums' bound
+    }
+    // sum |offset| < n max(L) / 2 < 2^e
+    int e = 0;
+    (void)frexp((double)n * 0.5 * std::max(p->L[0], std::max(p->L[1], p->L[2])), &e);
+    const int Fp = 93 - e;
+    hipLaunchKernelGGL(k_fof_accum, dim3(grid_for(un, p)), dim3(256), 0, s, pos, vel, (const unsigned*)root, (const int*)labels_out, un, g,
+                       Fp, (const unsigned long long*)&sm->vmax_bits, acc);
+    FB_LAUNCH_CHECK("k_fof_accum");
+    hipLaunchKernelGGL(k_fof_finish, dim3((nk + 255) / 256), dim3(256), 0, s, pos, (const unsigned*)sorted_roots,
+                       (const unsigned*)sorted_counts, nk, g, Fp, (const unsigned long long*)&sm->vmax_bits, un,
+                       (const unsigned long long*)acc, pos_out, vel ? vel_out : nullptr);
+    FB_LAUNCH_CHECK("k_fof_finish");
+    return FB_OK;
+}
+
+}  // extern "C"

@@ -207,6 +207,211 @@ class HaloDistribution(object):
         return HaloCatalogue(eng, buf, total)
 
 
+# ---------------------------------------------------------------------- friends-of-friends
+FOF_TILE = 64                       # particles per LDS tile of the pair search (FB_FOF_TILE of fb_fof.hip)
+RHO_CRIT = 2.77536627e11            # critical density today in h^2 Msun / Mpc^3
+
+
+class DeviceLabels(object):
+    """int32 per particle on the device; ``np.asarray(labels)`` is the host copy."""
+
+    def __init__(self, engine, buf, n):
+        self.engine, self._buf, self.n = engine, buf, int(n)
+        self._host = None
+
+    @property
+    def ptr(self):
+        return self._buf.ptr if self._buf is not None else None
+
+    def __len__(self):
+        return self.n
+
+    shape = property(lambda self: (self.n,))
+    dtype = np.dtype(np.int32)
+
+    def host(self):
+        if self._host is None:
+            h = np.empty(self.n, dtype=np.int32)
+            if self.n:
+                _lib.call("fb_memcpy_d2h", h.ctypes.data_as(ctypes.c_void_p), self.ptr, h.nbytes, self.engine.stream)
+            h.setflags(write=False)
+            self._host = h
+        return self._host
+
+    def __array__(self, dtype=None, copy=None):
+        h = self.host()
+        return h if dtype is None or np.dtype(dtype) == h.dtype else h.astype(dtype)
+
+
+class FoFHalos(HaloCatalogue):
+    """The friends-of-friends groups of ``find_halos_fof``, largest first: a HaloCatalogue of their centres of mass (Mpc, in
+    [0, L)) -- ``paint_catalogue`` takes it -- with ``count`` (members, host int64), ``mass`` (count x particle_mass, Msun),
+    ``velocities`` (mean member velocity, a HaloCatalogue, or None), ``labels`` (device int32 per particle: the rank of its
+    group in this catalogue, -1 if the group has fewer than nmin members), ``roots`` (least member index of each group, host
+    int64), ``n_groups_all`` (groups of any size), ``linking_length`` (Mpc) and ``particle_mass`` (Msun)."""
+
+    def __init__(self, engine, buf, n, count, roots, velocities, labels, n_groups_all, linking_length, particle_mass):
+        HaloCatalogue.__init__(self, engine, buf, n)
+        self.count, self.roots, self.velocities, self.labels = count, roots, velocities, labels
+        self.n_groups_all, self.linking_length, self.particle_mass = int(n_groups_all), float(linking_length), float(particle_mass)
+        self.mass = count.astype(np.float64) * float(particle_mass)
+
+    def __repr__(self):
+        return "FoFHalos(%d halos of %d groups, linking length %.6g Mpc)" % (self.n, self.n_groups_all, self.linking_length)
+
+
+def fof_linking_length(L, n, linking_length=0.2, absolute=False):
+    """The linking length in Mpc: ``linking_length`` itself, or that fraction of the mean spacing (Lx Ly Lz / n)^(1/3).
+    ValueError unless 0 < l < min(L) / 2."""
+    ell = float(linking_length) if absolute else float(linking_length) * (float(L[0]) * float(L[1]) * float(L[2]) / n) ** (1. / 3.)
+    if not (0. < ell < 0.5 * min(L)):
+        raise ValueError("linking length %.6g Mpc: must be above 0 and below half the shortest box side (%.6g Mpc)"
+                         % (ell, 0.5 * min(L)))
+    return ell
+
+
+def fof_cells(L, ell, n):
+    """Cells per axis of the pair search: side L_a / Nc_a >= l (1 + 1e-9), so that rounding in a particle's cell index cannot
+    separate friends by two cells; Nc_a <= max(4, floor((n / 2)^(1/3))): two particles per cell on average in a cubic box."""
+    cap = max(4, int(np.floor((0.5 * n) ** (1. / 3.))))
+    return tuple(max(1, min(int(np.floor(float(La) / ell * (1. - 1e-9))), cap)) for La in L)
+
+
+def fof_device_bytes(n, cells, nmin, host_positions=False, velocities=False):
+    """Device bytes find_halos_fof allocates beside the particles: the link's work buffer (permuted positions, permutation,
+    cell table), parents, counts, labels and the catalogue of at most n / nmin groups."""
+    ncells = int(cells[0]) * int(cells[1]) * int(cells[2])
+    nk = n // max(1, nmin)
+    need = int(_lib.load().fb_fof_work_bytes(int(n), ncells)) + 3 * 4 * n + 8 * nk + (256 + 96 * nk) + (8 + 48) * nk + 512
+    if host_positions:
+        need += 24 * n * (2 if velocities else 1)
+    return need
+
+
+def find_halos_fof(box, particles, linking_length=0.2, nmin=20, absolute=False, particle_mass=None, velocities=None,
+                   timings=None):
+    """Friends-of-friends halos of a particle set on the device (nbodykit's FOF; definition and design in DESIGN.md
+    section 4).  ``particles``: a ColaParticles (its velocities are used), a HaloCatalogue of this box (no velocities) or a
+    host (n, 3) array in Mpc with an optional host ``velocities`` (n, 3); positions are periodic in the box and wrapped on
+    read.  Two particles are friends iff their minimum-image distance is strictly below the linking length
+    ``linking_length`` x (Lx Ly Lz / n)^(1/3), or ``linking_length`` Mpc with ``absolute``; groups are the connected
+    components, and those of ``nmin`` members or more are returned as a ``FoFHalos``, by descending count, ties by ascending
+    least member index.  ``particle_mass`` (Msun; default Omega_m 2.77536627e11 h^2 Lx Ly Lz / n, Omega_m = Omega_c + Omega_b, with lengths in Mpc, this
+    package's unit -- not Mpc/h, so the mass is in Msun, not Msun/h).  ``timings``: a dict that receives the milliseconds of
+    the stages.  ValueError: a bad linking length, a position or velocity that is not finite, or a position too large to wrap
+    into the box (|x| >= 2^52 L); MemoryError before any
+    kernel runs if the work memory does not fit; RuntimeError if a union-find loop hits its iteration cap."""
+    import time
+    eng = box.engine
+    L = (float(box.Lx), float(box.Ly), float(box.Lz))
+    nmin = int(nmin)
+    if nmin < 1:
+        raise ValueError("nmin must be >= 1")
+    keep = []
+    host = not isinstance(particles, HaloCatalogue)
+    if not host:
+        if particles.engine is not eng:
+            raise ValueError("particles: a catalogue of this box")
+        if velocities is not None:
+            raise ValueError("velocities: only with host positions (a ColaParticles carries its own)")
+        n = particles.n
+        vcat = getattr(particles, "velocities", None)
+        vcat = vcat if isinstance(vcat, HaloCatalogue) and vcat.n == n else None
+    else:
+        p = np.ascontiguousarray(particles, dtype=np.float64)
+        if p.ndim != 2 or p.shape[1] != 3:
+            raise ValueError("particles: an (n, 3) array")
+        n = p.shape[0]
+        v = None
+        if velocities is not None:
+            v = np.ascontiguousarray(velocities, dtype=np.float64)
+            if v.shape != p.shape:
+                raise ValueError("velocities: expected shape %s, got %s" % (p.shape, v.shape))
+    if n > 2 ** 31 - 2:
+        raise ValueError("friends-of-friends: at most 2^31 - 2 particles")
+    ell = fof_linking_length(L, n, linking_length, absolute) if (n or absolute) else float("nan")
+    pmass = float(particle_mass) if particle_mass is not None else \
+        ((box.cosmo['Omega_c'] + box.cosmo['Omega_b']) * RHO_CRIT * box.cosmo['h'] ** 2 * L[0] * L[1] * L[2] / n if n else 0.)
+    has_vel = (v is not None) if host else (vcat is not None)
+
+    def empty(ngroups, labels):
+        vel = HaloCatalogue(eng, None, 0) if has_vel else None
+        return FoFHalos(eng, None, 0, np.zeros(0, dtype=np.int64), np.zeros(0, dtype=np.int64), vel, labels, ngroups, ell, pmass)
+
+    if n == 0:
+        return empty(0, DeviceLabels(eng, None, 0))
+    cells = fof_cells(L, ell, n)
+    need, have = fof_device_bytes(n, cells, nmin, host, has_vel), eng.free_bytes()
+    if need > have:
+        raise MemoryError("find_halos_fof: %d particles in %d x %d x %d cells take %.2f GiB of work memory, %.2f GiB are free"
+                          % ((n,) + cells + (need / 2. ** 30, have / 2. ** 30)))
+    if host:
+        pbuf = eng.upload_raw(p)
+        keep.append(pbuf)
+        pptr, vptr = pbuf.ptr, None
+        if v is not None:
+            vbuf = eng.upload_raw(v)
+            keep.append(vbuf)
+            vptr = vbuf.ptr
+    else:
+        pptr, vptr = particles.ptr, (vcat.ptr if vcat is not None else None)
+    try:
+        # 1-3. cells, pair search with union-find, flattening: the root of every particle
+        wbytes = int(eng.lib.fb_fof_work_bytes(n, cells[0] * cells[1] * cells[2]))
+        work, root = eng._alloc_bytes(wbytes), eng._alloc_bytes(4 * n)
+        bad = ctypes.c_int32(0)
+        nc = (ctypes.c_int32 * 3)(*cells)
+        ms = (ctypes.c_double * 4)()
+        _lib.call("fb_fof_link", eng._plan, pptr, n, ell, nc, work.ptr, wbytes, root.ptr, ctypes.byref(bad),
+                  ms if timings is not None else None, eng.stream)
+        if bad.value:
+            raise ValueError("find_halos_fof: a position is not finite, or too large to wrap into the box")
+        del work
+        t0 = time.perf_counter()
+        # 4. sizes; the (count, root) order of the groups kept is formed on the host
+        cap = n // nmin
+        count, small = eng._alloc_bytes(4 * n), eng._alloc_bytes(256)
+        kept = eng._alloc_bytes(8 * cap) if cap else None
+        out = (ctypes.c_int64 * 2)()
+        _lib.call("fb_fof_sizes", eng._plan, root.ptr, n, nmin, small.ptr, count.ptr, kept.ptr if cap else None, out, eng.stream)
+        ngroups, nk = int(out[0]), int(out[1])
+        del count
+        pairs = np.empty((nk, 2), dtype=np.uint32)
+        if nk:
+            _lib.call("fb_memcpy_d2h", pairs.ctypes.data_as(ctypes.c_void_p), kept.ptr, pairs.nbytes, eng.stream)
+            eng.sync()
+        del kept
+        order = np.lexsort((pairs[:, 0], -pairs[:, 1].astype(np.int64)))
+        sroots, scounts = np.ascontiguousarray(pairs[order, 0]), np.ascontiguousarray(pairs[order, 1])
+        labels = eng._alloc_bytes(4 * n)
+        cbuf = vout = None
+        if nk:
+            keep.extend([eng.upload_raw(sroots), eng.upload_raw(scounts)])
+            cbuf = eng._alloc_bytes(24 * nk)
+            vout = eng._alloc_bytes(24 * nk) if has_vel else None
+            cwork = eng._alloc_bytes(256 + 96 * nk)
+            args = (keep[-2].ptr, keep[-1].ptr, nk, cwork.ptr)
+        else:
+            args = (None, None, 0, None)
+        _lib.call("fb_fof_catalogue", eng._plan, pptr, vptr, root.ptr, n, *args, labels.ptr, cbuf.ptr if nk else None,
+                  vout.ptr if vout is not None else None, ctypes.byref(bad), eng.stream)
+        eng.sync()                          # host arrays behind the uploads must outlive the copies
+        if bad.value:
+            raise ValueError("find_halos_fof: a velocity is not finite, or n max |v| overflows")
+    except _lib.FastBoxError as e:
+        if e.code == -5:                    # FB_ERR_STATE: an iteration cap
+            raise RuntimeError("find_halos_fof: %s" % e)
+        raise
+    if timings is not None:
+        timings.update(bin_ms=ms[0], link_ms=ms[1] + ms[2], link_crowded_ms=ms[2], flatten_ms=ms[3], catalogue_ms=1e3 * (time.perf_counter() - t0),
+                       cells=cells)
+    lab = DeviceLabels(eng, labels, n)
+    if not nk:
+        return empty(ngroups, lab)
+    vel = HaloCatalogue(eng, vout, nk) if has_vel else None
+    return FoFHalos(eng, cbuf, nk, scounts.astype(np.int64), sroots.astype(np.int64), vel, lab, ngroups, ell, pmass)
+
+
 def paint(box, positions, weights=None, window='cic', compensated=False):
     """CosmoBox.paint_catalogue: see there."""
     eng, N = box.engine, box.N

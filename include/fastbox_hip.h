@@ -382,6 +382,37 @@ int fb_stack_voids(fb_plan* plan, const int32_t* labels, const void* field, cons
                    int64_t n_voids, const double* axes, const double* grid, int grid_pix, double* mean_out, int64_t* count_out,
                    int32_t* hit_out, void* stream);
 
+/* ---- friends-of-friends halos of a particle set (nbodykit's FOF; definition in DESIGN.md section 4) --------------------------
+ * One box on one GPU; particle data are fp64 whatever the plan's precision.  pos: DEVICE double[n][3] in Mpc, periodic in the
+ * plan's box, wrapped on read (w = x - L floor(x / L); w < 0: w += L; w >= L: w -= L).  i != j are friends iff
+ * d^2 = (dx dx + dy dy) + dz dz < link^2, d_a the minimum-image difference of the wrapped coordinates (d > L/2: d - L;
+ * d < -L/2: d + L); a group is a connected component, its root its least member index.  0 <= n <= 2^31 - 2.
+ * fb_fof_work_bytes: bytes of fb_fof_link's work buffer for n particles in ncells cells (-1: bad arguments).
+ * fb_fof_link: root_out (DEVICE uint32[n]) = the root of every particle.  ncell: HOST int[3], cells per axis, each of side
+ *   L_a / ncell_a >= link (so that friends lie in adjacent cells), at most 2^31 cells; 0 < link < min(L) / 2.  *bad = 1 (and
+ *   nothing linked) if a position is not finite, has |x| >= 2^52 L (where x - L floor(x / L) is off by units of ulp(x) >= L),
+ *   or does not wrap into [0, L) all the same: such a particle enters no cell.  stage_ms: HOST double[4] or NULL:
+ *   milliseconds of binning, the pair search of tile 0 of every cell, the pair search of the further tiles of the cells that
+ *   hold more than 64 particles, and flattening.  FB_ERR_STATE if a find / union loop (cap n + 1 steps, which a sound forest
+ *   cannot reach) or the flattening hits its iteration cap.  Synchronises.
+ * fb_fof_sizes: count_out (DEVICE uint32[n]) = members of the group at its root's index, 0 elsewhere; kept_out (DEVICE
+ *   uint32[floor(n / nmin)][2]) = (root, count) of the groups with count >= nmin, in arbitrary order; out_host[2] = the number
+ *   of groups of any size, the number kept.  work: DEVICE, 256 bytes.  Synchronises.
+ * fb_fof_catalogue: the n_kept groups in the caller's order (sorted_roots, sorted_counts: DEVICE uint32[n_kept]).
+ *   labels_out (DEVICE int32[n]) = the position of the particle's group in that order, -1 if it is not kept; pos_out (DEVICE
+ *   double[n_kept][3]) = wrap(a + mean_i(minimum-image(w_i - a))), a the root's wrapped position; vel_out the plain mean of
+ *   vel (DEVICE double[n][3]; NULL: none).  The sums are fixed-point (two 64-bit words, at least 93 - ceil(log2(n max(L) / 2))
+ *   fractional bits): the same bit for bit from call to call.  *bad = 4 if a velocity, or n max |v|, is not finite.  work: DEVICE,
+ *   256 + 96 n_kept bytes.  Synchronises only when vel is given.                                                              */
+int64_t fb_fof_work_bytes(int64_t n, int64_t ncells);
+int fb_fof_link(fb_plan* plan, const double* pos, int64_t n, double link, const int* ncell, void* work, int64_t work_bytes,
+                uint32_t* root_out, int* bad, double* stage_ms, void* stream);
+int fb_fof_sizes(fb_plan* plan, const uint32_t* root, int64_t n, int64_t nmin, void* work, uint32_t* count_out, uint32_t* kept_out,
+                 int64_t* out_host, void* stream);
+int fb_fof_catalogue(fb_plan* plan, const double* pos, const double* vel, const uint32_t* root, int64_t n,
+                     const uint32_t* sorted_roots, const uint32_t* sorted_counts, int64_t n_kept, void* work, int32_t* labels_out,
+                     double* pos_out, double* vel_out, int* bad, void* stream);
+
 /* ---- transfer functions (apply_transfer_fn box.py:374-379, smooth_field :651-653) ---------- */
 #define FB_FILT_TABLE 0          /* table: real multiplier, same layout as the field */
 #define FB_FILT_BEAM_HIGHPASS 1  /* (1-exp(-.5(|kpar|/p0)^p2)) [p0>0] * exp(-.5(kperp/p1)^2) [p1>0] */
