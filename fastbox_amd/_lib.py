@@ -105,6 +105,9 @@ SIGNATURES = {
     "fb_fof_sizes": (c_int, [c_void_p, c_void_p, c_i64, c_i64, c_void_p, c_void_p, c_void_p, ctypes.POINTER(c_i64), c_void_p]),
     "fb_fof_catalogue": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_i64, c_void_p, c_void_p,
                                  c_void_p, c_void_p, P_i32, c_void_p]),
+    "fb_pair_work_bytes": (c_i64, [c_i64, c_i64, c_i64]),
+    "fb_pair_count": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_int, P_double, c_int, c_int, c_double, P_i32, c_void_p,
+                              c_i64, c_void_p, P_i32, P_double, c_void_p]),
     "fb_real_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_void_p]),
     "fb_real_multiply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fb_real_to_complex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
@@ -167,6 +170,7 @@ SIGNATURES = {
     "fb_slab_exchange": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p]),
     "fb_allreduce_f64": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "fb_set_exp_shift": (c_int, [c_void_p, ctypes.c_double]),
+    "fb_debug_pair_flush": (c_int, [c_i64]),
     "fb_debug_strided_pass": (c_int, [c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "fb_debug_read_stamps": (c_int, [c_void_p, ctypes.POINTER(ctypes.c_longlong), c_i64]),
     "fb_profile_select": (c_int, [c_void_p, ctypes.c_uint]),

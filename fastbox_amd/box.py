@@ -1096,6 +1096,15 @@ class CosmoBox(object):
         from . import halos
         return halos.find_halos_fof(self, particles, **kw)
 
+    def pair_counts(self, first, second=None, edges=None, mode='1d', Nmu=10, pimax=None, poles=None):
+        """Additive: pair counts of one catalogue (or of ``first`` against ``second``) in bins of r, (r, mu) or (r_p, pi),
+        counted on the device, and xi = npairs / RR - 1 with the analytic RR of the periodic box -- what nbodykit's
+        ``SimulationBox2PCF`` gives (the reference's examples/example_corr_fn.py leaves it commented out).  Catalogues: a
+        ``FoFHalos``, ``ColaParticles`` or other HaloCatalogue of this box, or a host (n, 3) array.  Returns a ``PairCounts``.
+        Keywords and definition: ``fastbox_amd.halos.pair_counts``; DESIGN.md section 4."""
+        from . import halos
+        return halos.pair_counts(self, first, second=second, edges=edges, mode=mode, Nmu=Nmu, pimax=pimax, poles=poles)
+
     def sigmaR(self, R):
         """RMS of the field smoothed with a top-hat of R Mpc/h, from the binned power
         spectrum (box.py:657-683; scipy's simps is spelled simpson since 1.14)."""

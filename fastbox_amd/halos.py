@@ -412,6 +412,205 @@ def find_halos_fof(box, particles, linking_length=0.2, nmin=20, absolute=False, 
     return FoFHalos(eng, cbuf, nk, scounts.astype(np.int64), sroots.astype(np.int64), vel, lab, ngroups, ell, pmass)
 
 
+
+# ---------------------------------------------------------------------- pair counts
+PAIR_MODES = {"1d": 0, "2d": 1, "projected": 2}
+PAIR_MAX_NR, PAIR_MAX_BINS = 256, 4096          # FB_PAIR_MAX_NR, FB_PAIR_MAX_BINS of fb_pairs.hip
+_LEGENDRE = {0: lambda m: np.ones_like(m), 2: lambda m: 0.5 * (3. * m * m - 1.), 4: lambda m: 0.125 * ((35. * m * m - 30.) * m * m + 3.)}
+
+
+class PairCounts(object):
+    """Pair counts of one or two catalogues in the periodic box and the natural estimator with analytic RR on top of them
+    (``pair_counts``; DESIGN.md section 4).  Members: ``mode``; ``edges`` (r edges, or r_p edges for 'projected', Mpc);
+    ``r``, the arithmetic bin midpoints; ``mu_edges`` ('2d') or ``pi_edges`` ('projected'), else None; ``npairs`` int64 of
+    shape (nr,), (nr, Nmu) or (nr, npi): ordered pairs, so every auto count is even; ``rr`` = P V_bin / (Lx Ly Lz), P =
+    n (n - 1) for auto-counts and n1 n2 for cross-counts, V_bin = (4 pi / 3)(r1^3 - r0^3), times dmu for '2d', and
+    pi (r_p1^2 - r_p0^2) 2 dpi for 'projected'; ``xi`` = npairs / rr - 1 (NaN where rr = 0: an empty catalogue); ``poles``, a
+    dict l -> xi_l(r) = (2 l + 1) sum_m xi(r, mu_m) P_l(mu_m) dmu at the mu midpoints ('2d' with ``poles``; else {});
+    ``wp`` = 2 sum_pi xi(r_p, pi) dpi ('projected'; else None); ``n1``, ``n2``, ``auto``."""
+
+    def __init__(self, edges, npairs, L, n1, n2, auto, mode='1d', poles=None):
+        self.mode = mode
+        self.edges = np.array(edges, dtype=np.float64)
+        self.npairs = np.array(npairs, dtype=np.int64)
+        self.n1, self.n2, self.auto = int(n1), int(n2), bool(auto)
+        self.L = tuple(float(a) for a in L)
+        e = self.edges
+        nr = e.size - 1
+        if mode not in PAIR_MODES or self.npairs.ndim != (1 if mode == '1d' else 2) or self.npairs.shape[0] != nr:
+            raise ValueError("PairCounts: counts of shape (nr,) for '1d', (nr, nsub) for '2d' and 'projected'")
+        self.r = 0.5 * (e[1:] + e[:-1])
+        self.mu_edges = self.pi_edges = self.wp = None
+        P = float(self.n1) * float(self.n1 - 1) if self.auto else float(self.n1) * float(self.n2)
+        box_volume = self.L[0] * self.L[1] * self.L[2]
+        if mode == 'projected':
+            npi = self.npairs.shape[1]
+            self.pi_edges = np.arange(npi + 1, dtype=np.float64)
+            vol = (np.pi * (e[1:] ** 2 - e[:-1] ** 2))[:, None] * (2. * np.diff(self.pi_edges))[None, :]
+        else:
+            vol = (4. * np.pi / 3.) * (e[1:] ** 3 - e[:-1] ** 3)
+            if mode == '2d':
+                nmu = self.npairs.shape[1]
+                self.mu_edges = np.arange(nmu + 1, dtype=np.float64) / nmu
+                vol = vol[:, None] * np.diff(self.mu_edges)[None, :]
+        self.rr = P * vol / box_volume
+        with np.errstate(divide='ignore', invalid='ignore'):
+            self.xi = np.where(self.rr > 0., self.npairs / self.rr - 1., np.nan)
+        self.poles = {}
+        if poles is not None:
+            if mode != '2d':
+                raise ValueError("poles: with mode='2d' only")
+            mu = 0.5 * (self.mu_edges[1:] + self.mu_edges[:-1])
+            dmu = np.diff(self.mu_edges)
+            for l in _check_pair_poles(poles):
+                self.poles[l] = (2 * l + 1) * np.sum(self.xi * (_LEGENDRE[l](mu) * dmu)[None, :], axis=1)
+        if mode == 'projected':
+            self.wp = 2. * np.sum(self.xi * np.diff(self.pi_edges)[None, :], axis=1)
+
+    def __repr__(self):
+        return "PairCounts(%s, %s, n1=%d, n2=%d, bins %s)" % (self.mode, "auto" if self.auto else "cross", self.n1, self.n2,
+                                                             self.npairs.shape)
+
+
+def _check_pair_poles(poles):
+    ps = tuple(int(l) for l in poles)
+    if not ps or any(l not in (0, 2, 4) for l in ps) or len(set(ps)) != len(ps):
+        raise ValueError("poles: a subset of (0, 2, 4)")
+    return ps
+
+
+def pair_setup(L, N, edges=None, mode='1d', Nmu=10, pimax=None, poles=None):
+    """The checked arguments of ``pair_counts`` as (edges, nsub, sub_max, reach): nsub = 1, Nmu or int(pimax); reach = the
+    largest separation along each axis.  Default edges: 20 logarithmic bins from min(L) / N, one cell of the box's grid, to
+    min(L) / 8 (the minimum over x and y only for 'projected'); they exist for N > 8 only.  ValueError for anything ``pair_counts`` does not accept."""
+    L = tuple(float(a) for a in L)
+    if mode not in PAIR_MODES:
+        raise ValueError("mode must be one of %s" % sorted(PAIR_MODES))
+    if poles is not None:
+        if mode != '2d':
+            raise ValueError("poles: with mode='2d' only")
+        _check_pair_poles(poles)
+    if pimax is not None and mode != 'projected':
+        raise ValueError("pimax: with mode='projected' only")
+    lmin = min(L[:2]) if mode == 'projected' else min(L)
+    if edges is None:
+        if int(N) <= 8:
+            raise ValueError("edges: the default (min(L) / N to min(L) / 8) needs a box of N > 8 cells per side; pass edges")
+        edges = np.geomspace(lmin / int(N), lmin / 8., 21)
+    e = np.array(edges, dtype=np.float64)
+    if e.ndim != 1 or e.size < 2 or not np.all(np.isfinite(e)) or e[0] < 0. or not np.all(e[1:] > e[:-1]):
+        raise ValueError("edges: a strictly ascending array of at least 2 finite values, edges[0] >= 0")
+    nr = e.size - 1
+    if nr > PAIR_MAX_NR:
+        raise ValueError("edges: at most %d bins, got %d" % (PAIR_MAX_NR, nr))
+    if not e[-1] < 0.5 * lmin:
+        raise ValueError("edges: the last edge %.6g Mpc must be below half the shortest box side%s (%.6g Mpc)"
+                         % (e[-1], " across the line of sight" if mode == 'projected' else "", 0.5 * lmin))
+    nsub, sub_max, reach = 1, 0., (e[-1],) * 3
+    if mode == '2d':
+        if int(Nmu) != Nmu or int(Nmu) < 1:
+            raise ValueError("Nmu: a positive integer")
+        nsub = int(Nmu)
+    elif mode == 'projected':
+        if pimax is None or not np.isfinite(pimax) or pimax <= 0. or int(pimax) != pimax:
+            raise ValueError("pimax: a positive integer value in Mpc (one pi bin per Mpc)")
+        if not pimax < 0.5 * L[2]:
+            raise ValueError("pimax: %.6g Mpc must be below half the box side along the line of sight (%.6g Mpc)" % (pimax, 0.5 * L[2]))
+        nsub, sub_max = int(pimax), float(pimax)
+        reach = (e[-1], e[-1], sub_max)
+    if nr * nsub > PAIR_MAX_BINS:
+        raise ValueError("%d x %d bins: at most %d bins in total (and at most %d in r)" % (nr, nsub, PAIR_MAX_BINS, PAIR_MAX_NR))
+    return e, nsub, sub_max, reach
+
+
+def pair_cells(L, reach, n):
+    """Cells per axis of the pair sweep: side L_a / Nc_a >= reach_a (1 + 1e-9) as ``fof_cells`` has it, at least 2 per axis
+    (reach_a < L_a / 2; with 2 or 3 cells every cell is a neighbour, so the margin is not needed there) and at most
+    max(4, floor((n / 2)^(1/3)))."""
+    cap = max(4, int(np.floor((0.5 * n) ** (1. / 3.))))
+    return tuple(max(2, min(int(np.floor(float(La) / float(ra) * (1. - 1e-9))), cap)) for La, ra in zip(L, reach))
+
+
+def pair_device_bytes(n1, n2, cells, nbins=PAIR_MAX_BINS, host_first=False, host_second=False):
+    """Device bytes pair_counts allocates beside the catalogues: the work buffer (permuted positions, cell ids and cell
+    tables of both catalogues -- ``n2`` = 0 for auto-counts), the counts, and the uploads of host positions."""
+    ncells = int(cells[0]) * int(cells[1]) * int(cells[2])
+    need = int(_lib.load().fb_pair_work_bytes(int(n1), int(n2), ncells)) + 8 * int(nbins) + 512
+    return need + (24 * n1 + 32 if host_first else 0) + (24 * n2 + 32 if host_second else 0)
+
+
+def _pair_positions(eng, x, name):
+    """(n, host array or None, catalogue or None) of one input of pair_counts."""
+    if isinstance(x, HaloCatalogue):
+        if x.engine is not eng:
+            raise ValueError("%s: a catalogue of this box" % name)
+        return x.n, None, x
+    p = np.ascontiguousarray(x, dtype=np.float64)
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise ValueError("%s: an (n, 3) array" % name)
+    return p.shape[0], p, None
+
+
+def pair_counts(box, first, second=None, edges=None, mode='1d', Nmu=10, pimax=None, poles=None, timings=None):
+    """Pair counts in separation bins on the device, and the correlation function from them (nbodykit's
+    ``SimulationBox2PCF``; definition and design in DESIGN.md section 4).  ``first``, ``second``: a HaloCatalogue of this box
+    (FoFHalos, ColaParticles) or a host (n, 3) array in Mpc; positions are periodic in the box and wrapped on read, as in
+    ``find_halos_fof``.  ``second`` None, or the same object as ``first``: auto-counts (ordered pairs i != j); anything else,
+    a separate copy of the same positions included: cross-counts (all n1 n2 pairs).  ``mode``: '1d' bins in r; '2d' in
+    (r, mu), mu = |dz| / r in ``Nmu`` uniform bins (a pair at d = 0 goes to the last one); 'projected' in (r_p, pi), pi = |dz|
+    in int(pimax) bins of 1 Mpc -- the line of sight is z.  ``edges``: r (or r_p) edges in Mpc, lower edge inclusive, upper
+    exclusive, decided on squares; default and limits: ``pair_setup``.  ``poles``: a subset of (0, 2, 4), '2d' only.
+    ``timings``: a dict that receives the milliseconds of the stages.  Returns a ``PairCounts``.  ValueError: bad arguments
+    (before the device is touched), a position that is not finite or too large to wrap into the box (|x| >= 2^52 L);
+    MemoryError before any kernel runs if the work memory does not fit."""
+    eng = box.engine
+    L = (float(box.Lx), float(box.Ly), float(box.Lz))
+    e, nsub, sub_max, reach = pair_setup(L, getattr(box, "N", 1), edges, mode, Nmu, pimax, poles)
+    auto = second is None or second is first
+    n1, h1, c1 = _pair_positions(eng, first, "first")
+    n2, h2, c2 = (n1, None, None) if auto else _pair_positions(eng, second, "second")
+    if max(n1, n2) > 2 ** 31 - 2:
+        raise ValueError("pair counts: at most 2^31 - 2 particles in a catalogue")
+    nr = e.size - 1
+    nbins = nr * nsub
+    cells = pair_cells(L, reach, max(n1, n2, 1))
+    need, have = pair_device_bytes(n1, 0 if auto else n2, cells, nbins, h1 is not None, h2 is not None), eng.free_bytes()
+    if need > have:
+        raise MemoryError("pair_counts: %d and %d particles in %d x %d x %d cells take %.2f GiB of work memory, %.2f GiB are free"
+                          % ((n1, n2) + cells + (need / 2. ** 30, have / 2. ** 30)))
+    keep = []
+
+    def pointer(n, host, cat):
+        if n == 0:                      # an empty catalogue still needs an address: NULL means auto-counts
+            keep.append(eng._alloc_bytes(32))
+            return keep[-1].ptr
+        if cat is not None:
+            return cat.ptr
+        keep.append(eng.upload_raw(host))
+        return keep[-1].ptr
+
+    p1 = pointer(n1, h1, c1)
+    p2 = None if auto else pointer(n2, h2, c2)
+    wbytes = int(eng.lib.fb_pair_work_bytes(n1, 0 if auto else n2, cells[0] * cells[1] * cells[2]))
+    work, out = eng._alloc_bytes(wbytes), eng._alloc_bytes(8 * nbins)
+    e2 = np.ascontiguousarray(e * e)
+    bad = ctypes.c_int32(0)
+    nc = (ctypes.c_int32 * 3)(*cells)
+    ms = (ctypes.c_double * 3)()
+    _lib.call("fb_pair_count", eng._plan, p1, n1, p2, 0 if auto else n2, PAIR_MODES[mode],
+              e2.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), nr, nsub, sub_max, nc, work.ptr, wbytes, out.ptr, ctypes.byref(bad),
+              ms if timings is not None else None, eng.stream)
+    if bad.value:
+        raise ValueError("pair_counts: a position is not finite, or too large to wrap into the box")
+    counts = np.empty(nbins, dtype=np.uint64)
+    _lib.call("fb_memcpy_d2h", counts.ctypes.data_as(ctypes.c_void_p), out.ptr, counts.nbytes, eng.stream)
+    eng.sync()                          # host arrays behind the uploads must outlive the copies
+    if timings is not None:
+        timings.update(bin_ms=ms[0], count_ms=ms[1] + ms[2], count_crowded_ms=ms[2], cells=cells)
+    npairs = counts.astype(np.int64).reshape((nr,) if mode == '1d' else (nr, nsub))
+    return PairCounts(e, npairs, L, n1, n2, auto, mode=mode, poles=poles)
+
+
 def paint(box, positions, weights=None, window='cic', compensated=False):
     """CosmoBox.paint_catalogue: see there."""
     eng, N = box.engine, box.N

@@ -413,6 +413,29 @@ int fb_fof_catalogue(fb_plan* plan, const double* pos, const double* vel, const 
                      const uint32_t* sorted_roots, const uint32_t* sorted_counts, int64_t n_kept, void* work, int32_t* labels_out,
                      double* pos_out, double* vel_out, int* bad, void* stream);
 
+/* ---- pair counts in separation bins (nbodykit's SimulationBox2PCF) ------------------------------------
+ * One box on one GPU; particle data are fp64 whatever the plan's precision.  pos1, pos2: DEVICE double[n][3] in Mpc, periodic
+ * in the plan's box, wrapped on read and differenced by minimum image exactly as fb_fof_link does.  pos2 NULL: auto-counts
+ * (ordered pairs i != j of pos1, every unordered pair twice, no particle with itself, distinct particles at one position do
+ * pair; n2 is ignored); else cross-counts: all n1 n2 ordered pairs, coincident ones included.  0 <= n <= 2^31 - 2 each.
+ * mode 0: bins in r -- radial bin b holds a pair iff edges2[b] <= d^2 < edges2[b + 1], d^2 = (dx dx + dy dy) + dz dz;
+ *   nsub = 1.  mode 1: bins in (r, mu), mu bin m = the number of j in 1 .. nsub - 1 with dz dz (double)(nsub nsub) >=
+ *   (double)(j j) d^2, every product rounded on its own (a pair with d^2 = 0 lands in m = nsub - 1).  mode 2: bins in
+ *   (r_p, pi): r_p^2 = dx dx + dy dy takes the place of d^2 in the radial test, the pi bin is the number of j in
+ *   1 .. nsub - 1 with dz dz >= (double)(j j), and a pair with dz dz >= sub_max^2 is dropped; sub_max = pimax = nsub.
+ *   No square root is taken.  edges2: HOST double[nr + 1], the squares of the edges, strictly ascending from >= 0;
+ *   1 <= nr <= 256, nr nsub <= 4096.  The largest separation along every axis (sqrt(edges2[nr]); pimax along z in mode 2)
+ *   must stay below L_a / 2.  ncell: HOST int[3], cells per axis, at least 2 and of side L_a / ncell_a >= that separation.
+ * fb_pair_work_bytes: bytes of fb_pair_count's work buffer (n2 = 0 for auto-counts; -1: bad arguments).
+ * fb_pair_count: counts_out (DEVICE uint64[nr][nsub]) = the counts, all integer adds: the same bit for bit from call to
+ *   call.  *bad = 1 (and nothing counted) if a position of either catalogue is not finite or has |x| >= 2^52 L.  stage_ms: HOST
+ *   double[3] or NULL: milliseconds of binning, the sweep over tile 0 of every cell, and the sweep over the further tiles of
+ *   the cells that hold more than 64 particles.  Synchronises.                                                              */
+int64_t fb_pair_work_bytes(int64_t n1, int64_t n2, int64_t ncells);
+int fb_pair_count(fb_plan* plan, const double* pos1, int64_t n1, const double* pos2, int64_t n2, int mode, const double* edges2,
+                  int nr, int nsub, double sub_max, const int* ncell, void* work, int64_t work_bytes, uint64_t* counts_out,
+                  int* bad, double* stage_ms, void* stream);
+
 /* ---- transfer functions (apply_transfer_fn box.py:374-379, smooth_field :651-653) ---------- */
 #define FB_FILT_TABLE 0          /* table: real multiplier, same layout as the field */
 #define FB_FILT_BEAM_HIGHPASS 1  /* (1-exp(-.5(|kpar|/p0)^p2)) [p0>0] * exp(-.5(kperp/p1)^2) [p1>0] */
@@ -752,6 +775,10 @@ int fb_set_exp_shift(fb_plan* plan, double shift);
 /* tuning aid: a single strided FFT pass over a half spectrum (axis 0 = x, 1 = y;
  * mode 0 plain in place, 1 fused generator, 2 fused binning without store) */
 int fb_debug_strided_pass(fb_plan* plan, void* half, int axis, int mode, void* stream);
+/* testing aid: the number of pair tests after which a workgroup of fb_pair_count's sweep flushes its 32-bit LDS histogram
+ * to the global one (1 .. 2^31; 0: the default, 2^31, which no input of a few thousand points reaches).  Process-wide; the
+ * counts do not depend on it. */
+int fb_debug_pair_flush(int64_t pairs);
 /* diagnostic builds (-DFB_STAMPS) only: per-workgroup phase time stamps of the last plain pass */
 int fb_debug_read_stamps(fb_plan* plan, long long* host, int64_t count);
 
