@@ -2,6 +2,7 @@
 #include "../../include/fastbox_hip.h"
 #include "fb_plan.h"
 #include "fb_api_util.h"
+#include "fb_kshell.h"                   // FB_TWO_PI
 #include <dlfcn.h>
 #include <rccl/rccl.h>           // types and prototypes only: the functions are looked up in a dlopen'ed librccl (fb_comm.inc)
 #include <algorithm>
@@ -106,7 +107,7 @@ int fb_plan_create(fb_plan** plan, int N, double Lx, double Ly, double Lz, int p
     if (!r) {          // k_perp per (k_x, k_y), the value kperp_exact() forms on the device (IEEE sqrt, same order)
         std::vector<double> kp((size_t)N * N);
         for (int i = 0; i < N; ++i)
-            for (int j = 0; j < N; ++j) kp[(size_t)i * N + j] = 6.283185307179586476925286766559 * std::sqrt(axis2[i] + axis2[N + j]);
+            for (int j = 0; j < N; ++j) kp[(size_t)i * N + j] = FB_TWO_PI * std::sqrt(axis2[i] + axis2[N + j]);
         r = upload(&p->kperp_tab, kp.data(), kp.size());
     }
     p->prow = 2048;      // 8 four-wave workgroups per CU

@@ -1,4 +1,4 @@
-// Argument checks, precision dispatch and the device guard shared by the extern "C" sources (fb_api.hip, fb_halo.hip).
+// Argument checks, precision dispatch and the device guard shared by every source that defines extern "C" entry points.
 #pragma once
 #include "fb_plan.h"
 

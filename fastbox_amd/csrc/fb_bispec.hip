@@ -5,7 +5,8 @@
 #include "../../include/fastbox_hip.h"
 #include "fb_plan.h"
 #include "fb_api_util.h"
-#include "fb_field_kernels.h"
+#include "fb_dev.h"                      // mode_of, wave_sum, k_bin_finish
+#include "fb_fft.h"                      // cx<T>
 #include "fb_kshell.h"
 #include <algorithm>
 #include <cmath>
@@ -24,15 +25,6 @@ struct BkSplitArgs {
     int N, NZV, NZP, NR;
     int nb, b0, nq;                     // shells b0 .. b0 + nq - 1 are written (and summed) by this launch
 };
-
-__device__ __forceinline__ double bk_sq2(double a, double b) {
-#pragma clang fp contract(off)
-    return a * a + b * b;
-}
-__device__ __forceinline__ double bk_add_sq(double s, double c) {
-#pragma clang fp contract(off)
-    return s + c * c;
-}
 
 // Shell split.  One (k_x, k_y) row of the half spectrum per wave, lanes along k_z; every stored cell (padding included) of the
 // nq shell spectra is written: the mode where it belongs to the shell, zero elsewhere.  UNIT: the spectrum is 1 on every mode
@@ -54,14 +46,14 @@ void k_bk_split(const cx<T>* __restrict__ half, cx<T>* __restrict__ shells, long
     for (long long row = (long long)blockIdx.x * 4 + wave; row < nrows; row += (long long)gridDim.x * 4) {
         const int i = (int)(row / a.NR), j = (int)(row % a.NR);
         const bool live = j < N;                                      // (row N of a plane is padding)
-        const double kperp2 = live ? bk_sq2((double)mode_of(i, N) * a.kf[0], (double)mode_of(j, N) * a.kf[1]) : 0.0;
+        const double kperp2 = live ? sq2((double)mode_of(i, N) * a.kf[0], (double)mode_of(j, N) * a.kf[1]) : 0.0;
         const long long base = row * a.NZP;
         for (int l0 = 0; l0 < a.NZP; l0 += 64) {
             const int l = l0 + lane;
             const bool in = live && l < a.NZV;
             cx<T> d{0, 0};
             if (in) d = UNIT ? cx<T>{1, 0} : half[base + l];
-            const double k2 = bk_add_sq(kperp2, (double)l * a.kf[2]);  // l <= N / 2: the stored k_z are the non-negative ones
+            const double k2 = add_sq(kperp2, (double)l * a.kf[2]);  // l <= N / 2: the stored k_z are the non-negative ones
             int key = 0x7fffffff;                                     // padding: beyond every shell
             if (in) {
                 key = -1;                                             // k = 0, or below the first edge
@@ -232,7 +224,7 @@ int bk_split_launch(fb_plan* p, bool unit, const void* half, void* shells, const
                            partial, a); }
     FB_LAUNCH_CHECK("k_bk_split");
     { FbProfScope _ps(p, FBK_BIN, s);
-    hipLaunchKernelGGL(k_bin_finish, dim3(3 * a.nq), dim3(256), 0, s, partial, blocks, 3 * a.nq, out_dev); }
+    hipLaunchKernelGGL(k_bin_finish<>, dim3(3 * a.nq), dim3(256), 0, s, partial, blocks, 3 * a.nq, out_dev); }
     FB_LAUNCH_CHECK("k_bin_finish");
     return FB_OK;
 }
@@ -268,10 +260,7 @@ int bk_check(const fb_plan* p, const double* kedges, int nb, int nwork) {
     FB_REQUIRE(nb >= 1 && nb <= FB_BK_MAX_SHELLS, "nb must be in 1..32");
     FB_REQUIRE(nwork >= 1 && nwork <= FB_BK_SPLIT, "nwork must be in 1..4");
     FB_REQUIRE(p->N <= 1024, "the bispectrum takes grids up to 1024^3");
-    FB_REQUIRE(kedges[0] >= 0.0, "the first k edge must be >= 0");
-    for (int q = 0; q < nb; ++q) FB_REQUIRE(std::isfinite(kedges[q]), "k edges must be finite (the last may be inf)");
-    for (int q = 1; q <= nb; ++q) FB_REQUIRE(kedges[q] > kedges[q - 1], "k edges must be strictly ascending");
-    return FB_OK;
+    return kshell_check_edges(kedges, nb);
 }
 
 int bispectrum(fb_plan* p, const void* real, void* work_half, void* work_shells, int nwork, void* cubes, const double* kedges,
@@ -292,7 +281,7 @@ int bispectrum(fb_plan* p, const void* real, void* work_half, void* work_shells,
     BkSplitArgs a;
     for (int q = 0; q <= nb; ++q) a.thr[q] = sq_threshold(kedges[q]);
     for (int q = nb + 1; q <= FB_BK_MAX_SHELLS; ++q) a.thr[q] = INFINITY;
-    for (int q = 0; q < 3; ++q) a.kf[q] = 6.283185307179586 / p->L[q];   // 2 * np.pi / L_a
+    fill_kf(p, a.kf);
     a.N = p->N; a.NZV = p->NZV; a.NZP = p->NZP; a.NR = p->NR; a.nb = nb;
     for (int b0 = 0; b0 < nb; b0 += nwork) {
         a.b0 = b0; a.nq = std::min(nwork, nb - b0);

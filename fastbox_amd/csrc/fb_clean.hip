@@ -9,6 +9,7 @@
 #include "../../include/fastbox_hip.h"
 #include "fb_plan.h"
 #include "fb_api_util.h"
+#include "fb_dev.h"
 #include <cmath>
 
 #define FB_CLEAN_KMAX 16                 // components (NMF) / sources (ICA)
@@ -16,12 +17,7 @@
 #define FB_CLEAN_RED_BLOCKS 1024         // workgroups of the grid-stride reductions
 
 namespace {
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
+using namespace fb;
 
 // One cyclic coordinate-descent pass over the k coefficients v[] of one row (scikit-learn's _update_cdnmf_fast, no
 // regularisation, no shuffling): b[t] = the row of X H^T (or X^T W), A = H H^T (or W^T W), k x k in LDS.
@@ -95,7 +91,7 @@ __global__ __launch_bounds__(256) void k_nmf_sweep(const T* __restrict__ cube, d
                 double a = 0.0;
 #pragma unroll
                 for (int q = 0; q < CPL; ++q) { const int c = lane + 64 * q; if (c < N) a += H[(size_t)t * N + c] * x[q]; }
-                b[t] = wsum(a);
+                b[t] = wave_sum(a);
                 if (live) w[t] = W[(size_t)t * npix + p];
             }
         }
@@ -213,7 +209,7 @@ __global__ __launch_bounds__(256) void k_nmf_residual(const T* __restrict__ cube
             if (c < N) { ss += r[q] * r[q]; if (out) out[p * N + c] = (T)r[q]; }
         }
     }
-    ss = wsum(ss);
+    ss = wave_sum(ss);
     if (lane == 0) red[wave] = ss;
     __syncthreads();
     if (threadIdx.x == 0) partial[blockIdx.x] = (red[0] + red[1]) + (red[2] + red[3]);
@@ -230,7 +226,7 @@ __global__ __launch_bounds__(256) void k_rows_posneg(const double* __restrict__ 
             const double v = a[(size_t)j * npix + p];
             if (v > 0.0) sp += v * v; else sn += v * v;
         }
-        sp = wsum(sp); sn = wsum(sn);
+        sp = wave_sum(sp); sn = wave_sum(sn);
         if (lane == 0) { red[wave][0] = sp; red[wave][1] = sn; }
         __syncthreads();
         if (threadIdx.x < 2)
@@ -262,9 +258,8 @@ __global__ __launch_bounds__(256) void k_min_finite(const T* __restrict__ x, lon
         if (!isfinite(v)) bad += 1.0;
         if (v < mn) mn = v;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) { const double u = __shfl_xor(mn, o, 64); mn = u < mn ? u : mn; }
-    bad = wsum(bad);
+    mn = wave_min_cmp(mn);
+    bad = wave_sum(bad);
     if (lane == 0) { red[wave][0] = mn; red[wave][1] = bad; }
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -365,7 +360,7 @@ __global__ __launch_bounds__(256) void k_ica_sources(const double* __restrict__ 
 #pragma unroll
     for (int i = 0; i < FB_CLEAN_KMAX; ++i) {
         if (i < n) {
-            const double a = wsum(s1[i]), b = wsum(s2[i]);
+            const double a = wave_sum(s1[i]), b = wave_sum(s2[i]);
             if (lane == 0) { red[wave][i] = a; red[wave][FB_CLEAN_KMAX + i] = b; }
         }
     }
@@ -396,7 +391,7 @@ __global__ __launch_bounds__(256) void k_rotate_spectra(const T* __restrict__ cu
             double a = 0.0;
 #pragma unroll
             for (int q = 0; q < CPL; ++q) { const int c = lane + 64 * q; if (c < N) a += row[c] * x[q]; }
-            a = wsum(a);
+            a = wave_sum(a);
             if (lane == j) keep = a;
         }
         if (lane < mend) B[p * N + m0 + lane] = keep;

@@ -10,24 +10,19 @@
 #include "../../include/fastbox_hip.h"
 #include "fb_plan.h"
 #include "fb_api_util.h"
+#include "fb_dev.h"
 #include <algorithm>
 #include <cmath>
 
 namespace {
+using namespace fb;
 
 constexpr double kTwoPi = 6.283185307179586;     // the double 2 * np.pi
 
-__device__ __forceinline__ int signed_mode(int i, int N) { return i < N / 2 ? i : i - N; }     // N/2 -> -N/2 (fftfreq)
-__device__ __forceinline__ long long wrap_node(long long m, int N) {
-    m %= N;                                       // bounded whatever the position held
-    return m < 0 ? m + N : m;
-}
-__device__ __forceinline__ double wrap_pos(double x, double L) {
-    x = x - L * floor(x / L);
-    if (x < 0.0) x += L;
-    if (x >= L) x -= L;
-    return x;
-}
+// N/2 -> -N/2 (fftfreq).  For N >= 0 these are the values of mode_of (fb_dev.h); it stays here, written with the `N / 2` that
+// k_cola_kmul's plane tests (m == -N / 2) use, so that the convention and its tests read as one.  The mode that does differ
+// is k_paint_compensate's (fb_halo.hip): it keeps +N/2.
+__device__ __forceinline__ int signed_mode(int i, int N) { return i < N / 2 ? i : i - N; }
 
 // out = c * in on a half spectrum: b < 0: c i k_a / k^2 (zero at k = 0 and on the plane m_a = -N/2);
 // b >= 0: c k_a k_b / k^2 (zero at k = 0; for a != b also on the planes m_a = -N/2 and m_b = -N/2).  k_a = 2 pi m_a / L.
@@ -150,10 +145,6 @@ __global__ __launch_bounds__(256) void k_cola_vgrid(T* __restrict__ num, const T
     }
 }
 
-int grid_for(unsigned long long n, const fb_plan* p) {
-    const unsigned long long b = (n + 255) / 256, cap = 8ull * p->num_cu * 8;
-    return (int)std::max(1ull, std::min(b, cap));
-}
 unsigned long long n3_of(const fb_plan* p) { return (unsigned long long)p->N * p->N * p->N; }
 
 template <typename T>

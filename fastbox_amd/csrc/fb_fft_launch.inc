@@ -30,13 +30,9 @@ int gen_amplitude(const fb_plan* p, StridedOp<real_t>& op) {
     return FB_OK;
 }
 
+// room for `need` doubles in one of the plan's grow-only partials buffers
 int ensure(double** buf, size_t* cap, size_t need) {
-    if (*cap >= need) return FB_OK;
-    if (*buf) FB_HIP(hipFree(*buf));
-    *buf = nullptr; *cap = 0;
-    FB_HIP(hipMalloc(reinterpret_cast<void**>(buf), need * sizeof(double)));
-    *cap = need;
-    return FB_OK;
+    return ensure_bytes(reinterpret_cast<void**>(buf), cap, need * sizeof(double));
 }
 
 // PERSIST: resident workgroups that walk the tiles (k_fft_strided); 0: one workgroup per tile.  BLK: slab addressing.

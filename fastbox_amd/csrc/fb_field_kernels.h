@@ -7,14 +7,13 @@
 //                                per x-plane of which N are used
 //   full  : cx<T>  [N][N][N]
 #pragma once
+#include "fb_dev.h"                      // mode_of, wave_sum, wave_minmax, k_bin_finish
 #include "fb_fft.h"
+#include "fb_kshell.h"                   // FB_TWO_PI
 #include "fb_rng.h"
 
 namespace fb {
 
-#define FB_TWO_PI 6.283185307179586
-
-__device__ __forceinline__ int mode_of(int i, int N) { return i < (N >> 1) ? i : i - N; }   // box.py:119
 __device__ __forceinline__ int mirror_of(int i, int N) { return i == 0 ? 0 : N - i; }
 
 // Geometry tables computed on the host with the reference's own numpy
@@ -152,28 +151,6 @@ __device__ __forceinline__ int bin_of_mode(const BinGeom& bg, const KGeom& g, co
     return bin_exact(lbins, bg.nbins, kmag_exact(g, i, j, l));
 }
 
-// out[q] = sum over workgroups of partial[q][workgroup]; fixed order (thread-strided chains, LDS tree)
-static __global__ __launch_bounds__(256) void k_bin_finish(const double* __restrict__ partial, int nblocks, int nvals,
-                                                           double* __restrict__ out) {
-    __shared__ double sh[256];
-    const int q = blockIdx.x;
-    const double* src = partial + (size_t)q * nblocks;
-    double c[4] = {0, 0, 0, 0};
-    int r = threadIdx.x;
-    for (; r + 3 * 256 < nblocks; r += 4 * 256) {
-#pragma unroll
-        for (int u = 0; u < 4; ++u) c[u] += src[r + u * 256];
-    }
-    for (int u = 0; r < nblocks; r += 256, ++u) c[u & 3] += src[r];
-    sh[threadIdx.x] = (c[0] + c[1]) + (c[2] + c[3]);
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if ((int)threadIdx.x < o) sh[threadIdx.x] += sh[threadIdx.x + o];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[q] = sh[0];
-}
-
 // number of full-grid modes per bin (data independent; done once per bin set)
 static __global__ void k_bin_count(unsigned long long* __restrict__ counts, KGeom g, BinGeom bg) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -195,43 +172,7 @@ static __global__ void k_bin_count(unsigned long long* __restrict__ counts, KGeo
     for (int q = tid; q < bg.nbins; q += blockDim.x) if (lc[q]) atomicAdd(&counts[q], lc[q]);
 }
 
-// ---- reductions ---------------------------------------------------------------------------------
-// Sum over the 64 lanes, returned in every lane.  float: six DPP adds (row_shr 1, 2, 4, 8, then
-// row_bcast 15 and 31 carry the row totals forward; lanes a step does not reach add the `old`
-// operand 0), total in lane 63, one v_readlane -- no LDS crossbar round trips.
-__device__ __forceinline__ float wave_sum(float v) {
-#define FB_DPP_ADD(ctrl, rmask, bmask) \
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), ctrl, rmask, bmask, false))
-    FB_DPP_ADD(0x111, 0xf, 0xf);     // row_shr:1
-    FB_DPP_ADD(0x112, 0xf, 0xf);     // row_shr:2
-    FB_DPP_ADD(0x114, 0xf, 0xe);     // row_shr:4, lanes 4..15 of each row
-    FB_DPP_ADD(0x118, 0xf, 0xc);     // row_shr:8, lanes 8..15 of each row
-    FB_DPP_ADD(0x142, 0xa, 0xf);     // row_bcast:15 into rows 1 and 3
-    FB_DPP_ADD(0x143, 0xc, 0xf);     // row_bcast:31 into rows 2 and 3
-#undef FB_DPP_ADD
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-// min / max of an int over the wave (same DPP ladder as wave_sum; `old` = the identity element)
-template <bool MAX>
-__device__ __forceinline__ int wave_minmax(int v) {
-    constexpr int ident = MAX ? (int)0x80000000 : 0x7fffffff;
-#define FB_DPP_MM(ctrl, rmask, bmask) do { \
-        const int o = __builtin_amdgcn_update_dpp(ident, v, ctrl, rmask, bmask, false); \
-        v = MAX ? (o > v ? o : v) : (o < v ? o : v); } while (0)
-    FB_DPP_MM(0x111, 0xf, 0xf);
-    FB_DPP_MM(0x112, 0xf, 0xf);
-    FB_DPP_MM(0x114, 0xf, 0xe);
-    FB_DPP_MM(0x118, 0xf, 0xc);
-    FB_DPP_MM(0x142, 0xa, 0xf);
-    FB_DPP_MM(0x143, 0xc, 0xf);
-#undef FB_DPP_MM
-    return __builtin_amdgcn_readlane(v, 63);
-}
+// ---- reductions (the wave sums and min / max: fb_dev.h) --------------------------------------------
 
 __device__ __forceinline__ int shell_bin(const int* lthr, int nbins, int n2) {
     int lo = 0, hi = nbins;                       // number of thr[] <= n2
@@ -282,10 +223,7 @@ __global__ __launch_bounds__(256) void k_reduce_real(const T* __restrict__ in, T
         if (OP == 3) s = (double)x > s ? (double)x : s;        // (a NaN never wins: the maximum of the finite values)
         else s += (double)x;
     }
-    if (OP == 3) {
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) { const double t = __shfl_xor(s, o, 64); s = t > s ? t : s; }
-    } else s = wave_sum(s);
+    s = OP == 3 ? wave_max_cmp(s) : wave_sum(s);
     if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = s;
     __syncthreads();
     if (threadIdx.x == 0) {

@@ -143,7 +143,7 @@ int FBI(bin_power)(fb_plan* p, const void* half, int layout, int filter_kind, co
                        p->partials, geom(p), bin_geom(p), f, layout ? 0 : 1); }
     FB_LAUNCH_CHECK("k_bin_rows");
     { FbProfScope _ps(p, FBK_BIN, s);
-    hipLaunchKernelGGL(k_bin_finish, dim3(2 * nb), dim3(256), 0, s, p->partials, blocks, 2 * nb, sums_dev); }
+    hipLaunchKernelGGL(k_bin_finish<>, dim3(2 * nb), dim3(256), 0, s, p->partials, blocks, 2 * nb, sums_dev); }
     FB_LAUNCH_CHECK("k_bin_finish");
     return FB_OK;
 }
@@ -351,12 +351,8 @@ int FBI(sep_bin)(fb_plan* p, const void* real, const double* edges_dev, double e
     long long blocks = (rows + FB_SEP_WAVES - 1) / FB_SEP_WAVES;
     if (blocks > p->prow) blocks = p->prow;
     if (blocks < 1) blocks = 1;
-    const size_t need = (size_t)blocks * nv * nbins;
-    if (need > p->sep_partials_cap) {
-        if (p->sep_partials) { FB_HIP(hipFree(p->sep_partials)); p->sep_partials = nullptr; p->sep_partials_cap = 0; }
-        FB_HIP(hipMalloc((void**)&p->sep_partials, need * sizeof(double)));
-        p->sep_partials_cap = need;
-    }
+    const int rb = ensure_bytes((void**)&p->sep_partials, &p->sep_partials_cap, (size_t)blocks * nv * nbins * sizeof(double));
+    if (rb) return rb;
     if (lds > 65536) {             // more than 2 x 256 bins x 3 multipoles: up to 106 KiB of the CU's 160 KiB (nbins <= 1024)
         FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sep_bin<real_t, true>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -372,7 +368,7 @@ int FBI(sep_bin)(fb_plan* p, const void* real, const double* edges_dev, double e
                            p->sep_partials, sg); }
     FB_LAUNCH_CHECK("k_sep_bin");
     { FbProfScope _ps(p, FBK_BIN, s);
-    hipLaunchKernelGGL(k_bin_finish, dim3(nv * nbins), dim3(256), 0, s, p->sep_partials, (int)blocks, nv * nbins, out_dev); }
+    hipLaunchKernelGGL(k_bin_finish<>, dim3(nv * nbins), dim3(256), 0, s, p->sep_partials, (int)blocks, nv * nbins, out_dev); }
     FB_LAUNCH_CHECK("k_bin_finish");
     return FB_OK;
 }

@@ -167,40 +167,30 @@ __global__ __launch_bounds__(256) void k_fof_vmax(const double* vel, unsigned lo
         const double a = fabs(vel[i]);
         if (!(a < INFINITY)) bad = true; else m = fmax(m, a);
     }
-    for (int o = 32; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o));
+    m = wave_max(m);
     if ((threadIdx.x & 63) == 0) atomicMax(vmax_bits, (unsigned long long)__double_as_longlong(m));
     if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(err, FB_FOF_ERR_VEL);
 }
-// Fixed point, as k_paint of fb_halo.hip on double-precision plans: a contribution x is added as the integer round(x 2^F) split
-// into hi = floor(x 2^(F - 32)) and lo = x 2^F - hi 2^32 in [0, 2^32], two 64-bit accumulators -- integer adds, so the sums do
-// not depend on the order of the particles.  F = 93 - e with (number of particles) (bound of |x|) < 2^e: hi stays below 2^61.
-__device__ __forceinline__ int fof_exponent(double bound) {
-    int e = 0;
-    if (bound > 0.0) (void)frexp(bound, &e);
-    return 93 - e;
-}
+// Fixed point in two 64-bit accumulators (fb_dev.h): the sums do not depend on the order of the particles.  F = 93 - e with
+// (number of particles) (bound of |x|) < 2^e: hi stays below 2^61.
 __device__ __forceinline__ void fof_add(unsigned long long* acc, double x, int F) {
-    const double v = ldexp(x, F);
-    const double hi = floor(v * 2.3283064365386963e-10);
-    const double lo = v - hi * 4294967296.0;
-    atomicAdd(acc, (unsigned long long)(long long)hi);
-    atomicAdd(acc + 1, (unsigned long long)__double2ll_rn(lo));
-}
-__device__ __forceinline__ double fof_sum(const unsigned long long* acc, int F) {
-    return ldexp((double)(long long)acc[0] * 4294967296.0 + (double)acc[1], -F);
+    unsigned long long hi, lo;
+    fx_split(ldexp(x, F), hi, lo);
+    atomicAdd(acc, hi);
+    atomicAdd(acc + 1, lo);
 }
 // acc[g][6][2]: per group kept, the sums of the minimum-image offsets from the root's wrapped position and of the velocities
 __global__ __launch_bounds__(256) void k_fof_accum(const double* pos, const double* vel, const unsigned* root, const int* labels,
                                                    unsigned long long n, FofGeom g, int Fp, const unsigned long long* vmax_bits,
                                                    unsigned long long* acc) {
-    const int Fv = vel ? fof_exponent((double)n * __longlong_as_double((long long)vmax_bits[0])) : 0;
+    const int Fv = vel ? fx_exponent((double)n * __longlong_as_double((long long)vmax_bits[0]), 93) : 0;
     for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
         const int lab = labels[i];
         if (lab < 0) continue;
         const unsigned long long r = root[i];
         unsigned long long* a = acc + 12ull * (unsigned)lab;
         for (int c = 0; c < 3; ++c) {
-            const double d = fof_min_image(fof_wrap(pos[3 * i + c], g.L[c]) - fof_wrap(pos[3 * r + c], g.L[c]), g.L[c]);
+            const double d = fof_min_image(wrap_pos(pos[3 * i + c], g.L[c]) - wrap_pos(pos[3 * r + c], g.L[c]), g.L[c]);
             fof_add(a + 2 * c, d, Fp);
             if (vel) fof_add(a + 6 + 2 * c, vel[3 * i + c], Fv);
         }
@@ -211,13 +201,13 @@ __global__ __launch_bounds__(256) void k_fof_finish(const double* pos, const uns
                                                     const unsigned long long* acc, double* com, double* vmean) {
     const unsigned r = blockIdx.x * 256 + threadIdx.x;
     if (r >= nk) return;
-    const int Fv = vmean ? fof_exponent((double)n * __longlong_as_double((long long)vmax_bits[0])) : 0;
+    const int Fv = vmean ? fx_exponent((double)n * __longlong_as_double((long long)vmax_bits[0]), 93) : 0;
     const double m = (double)scount[r];
     const unsigned long long i = sroot[r];
     for (int c = 0; c < 3; ++c) {
-        const double a = fof_wrap(pos[3 * i + c], g.L[c]);
-        com[3ull * r + c] = fof_wrap(a + fof_sum(acc + 12ull * r + 2 * c, Fp) / m, g.L[c]);
-        if (vmean) vmean[3ull * r + c] = fof_sum(acc + 12ull * r + 6 + 2 * c, Fv) / m;
+        const double a = wrap_pos(pos[3 * i + c], g.L[c]);
+        com[3ull * r + c] = wrap_pos(a + fx_join(acc[12ull * r + 2 * c], acc[12ull * r + 2 * c + 1], Fp) / m, g.L[c]);
+        if (vmean) vmean[3ull * r + c] = fx_join(acc[12ull * r + 6 + 2 * c], acc[12ull * r + 6 + 2 * c + 1], Fv) / m;
     }
 }
 
@@ -231,7 +221,7 @@ FofWork work_layout(unsigned long long n, unsigned long long ncells) {
     w.spos = o; o += align16((size_t)n * 24);
     w.start = o; o += align16((size_t)(ncells + 1) * 4);
     w.cursor = o; o += align16((size_t)ncells * 4);
-    w.csum = o; o += align16((size_t)scan_chunks(ncells + 1) * 4);
+    w.csum = o; o += align16((size_t)scan_chunks(ncells) * 4);
     w.cellid = o; o += align16((size_t)n * 4);
     w.perm = o; o += align16((size_t)n * 4);
     w.items = o; o += align16((size_t)(n / FB_FOF_TILE + 1) * 8);
@@ -297,13 +287,8 @@ int fb_fof_link(fb_plan* p, const double* pos, int64_t n, double link, const int
     int r = read_small(sm, &h, s);
     if (r) return r;
     if (h.err & FB_FOF_ERR_POS) { *bad = 1; return FB_OK; }          // before any linking
-    const int nch = (int)scan_chunks(ncells + 1);
-    hipLaunchKernelGGL(k_fof_scan_chunks, dim3(nch), dim3(256), 0, s, (const unsigned*)cursor, ncells, csum);
-    FB_LAUNCH_CHECK("k_fof_scan_chunks");
-    hipLaunchKernelGGL(k_fof_scan_top, dim3(1), dim3(256), 0, s, csum, nch);
-    FB_LAUNCH_CHECK("k_fof_scan_top");
-    hipLaunchKernelGGL(k_fof_scan_apply, dim3(nch), dim3(256), 0, s, (const unsigned*)cursor, ncells, (const unsigned*)csum, start);
-    FB_LAUNCH_CHECK("k_fof_scan_apply");
+    r = exscan(ScanPlain{cursor}, ncells, csum, start, s);           // start[ncells] = n
+    if (r) return r;
     FB_HIP(hipMemsetAsync(cursor, 0, (size_t)ncells * 4, s));
     hipLaunchKernelGGL(k_fof_scatter, dim3(grid_for(un, p)), dim3(256), 0, s, pos, un, g, (const unsigned*)cellid, (const unsigned*)start,
                        cursor, perm, spos, (unsigned*)root_out);

@@ -8,6 +8,8 @@
 #include "../../include/fastbox_hip.h"
 #include "fb_plan.h"
 #include "fb_api_util.h"
+#include "fb_dev.h"
+#include "fb_scan.h"
 #include "fb_rng.h"
 #include <algorithm>
 #include <cmath>
@@ -19,6 +21,7 @@
 #define FB_HALO_LAM_MAX 16777216.0       // 2^24: every count below it is exact in fp32
 
 namespace {
+using namespace fb;
 
 // nbar / bias: a scalar, a profile along z (fp64 [N]), a field of the plan's precision or an fp64 field ([N^3])
 struct HPrm { const void* p; double v; int kind; };
@@ -30,25 +33,6 @@ __device__ __forceinline__ double hprm_at(const HPrm& q, unsigned long long i, i
         case FB_HALO_FIELD: return (double)((const T*)q.p)[i];
         default: return ((const double*)q.p)[i];
     }
-}
-
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-__device__ __forceinline__ double wave_max(double v) {
-    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-    return v;
-}
-// 256-lane workgroup reduction; the result in every lane.  op 0: sum, 1: max
-__device__ double block_reduce(double v, int op) {
-    __shared__ double red[4];
-    v = op ? wave_max(v) : wave_sum(v);
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    const double r = op ? fmax(fmax(red[0], red[1]), fmax(red[2], red[3])) : (red[0] + red[1]) + (red[2] + red[3]);
-    return r;
 }
 
 // log-normal statistics: per-workgroup max of bias*delta (op 1) or sum of exp(bias*delta - shift[0]) (op 0)
@@ -195,66 +179,11 @@ __global__ __launch_bounds__(256) void k_cat_hist(const T* counts, unsigned long
     for (int c = threadIdx.x; c <= kl; c += 256) H[(unsigned long long)c * nb + blockIdx.x] = h[c];
 }
 
-// exclusive scan S[j] = sum_{j' < j} c(j') H[j'], c(j) = j / nb, in three steps: chunk sums, a scan of the chunk sums in one
-// workgroup, the chunks themselves.  CH = 256 lanes x 16 entries.
-#define FB_SCAN_PER 16
-#define FB_SCAN_CH (256 * FB_SCAN_PER)
-__device__ __forceinline__ unsigned long long scan_w(const unsigned* H, unsigned long long j, unsigned long long M, int nb) {
-    return j < M ? (unsigned long long)(j / (unsigned)nb) * H[j] : 0ull;
-}
-__global__ __launch_bounds__(256) void k_scan_chunks(const unsigned* H, unsigned long long M, int nb, unsigned long long* csum) {
-    const unsigned long long j0 = (unsigned long long)blockIdx.x * FB_SCAN_CH;
-    unsigned long long s = 0;
-    for (int q = 0; q < FB_SCAN_PER; ++q) s += scan_w(H, j0 + (unsigned long long)q * 256 + threadIdx.x, M, nb);
-    __shared__ unsigned long long tot;
-    if (threadIdx.x == 0) tot = 0;
-    __syncthreads();
-    atomicAdd(&tot, s);
-    __syncthreads();
-    if (threadIdx.x == 0) csum[blockIdx.x] = tot;
-}
-// exclusive scan of v[0..256) in LDS (Hillis-Steele), returns this lane's prefix; `total` receives the sum
-__device__ unsigned long long block_exscan(unsigned long long v, unsigned long long* total) {
-    __shared__ unsigned long long sh[256];
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-        const unsigned long long a = threadIdx.x >= (unsigned)o ? sh[threadIdx.x - o] : 0ull;
-        __syncthreads();
-        sh[threadIdx.x] += a;
-        __syncthreads();
-    }
-    const unsigned long long incl = sh[threadIdx.x];
-    *total = sh[255];
-    __syncthreads();
-    return incl - v;
-}
-// one workgroup: csum[0..nc) -> exclusive prefix sums in place; csum[nc] = total
-__global__ __launch_bounds__(256) void k_scan_top(unsigned long long* csum, int nc) {
-    unsigned long long carry = 0;
-    for (int base = 0; base < nc; base += 256) {
-        const int i = base + threadIdx.x;
-        const unsigned long long v = i < nc ? csum[i] : 0ull;
-        unsigned long long tot;
-        const unsigned long long ex = block_exscan(v, &tot);
-        if (i < nc) csum[i] = carry + ex;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) csum[nc] = carry;
-}
-// lane t of chunk r takes the 16 consecutive entries j0 + 16 t ..
-__global__ __launch_bounds__(256) void k_scan_apply(const unsigned* H, unsigned long long M, int nb, const unsigned long long* csum,
-                                                    unsigned long long* S) {
-    const unsigned long long j0 = (unsigned long long)blockIdx.x * FB_SCAN_CH + (unsigned long long)threadIdx.x * FB_SCAN_PER;
-    unsigned long long w[FB_SCAN_PER], s = 0;
-    for (int q = 0; q < FB_SCAN_PER; ++q) { w[q] = scan_w(H, j0 + q, M, nb); s += w[q]; }
-    unsigned long long tot;
-    unsigned long long run = csum[blockIdx.x] + block_exscan(s, &tot);
-    for (int q = 0; q < FB_SCAN_PER; ++q) {
-        if (j0 + q < M) S[j0 + q] = run;
-        run += w[q];
-    }
-}
+// the catalogue's scan (fb_scan.h): S[j] = sum_{j' < j} c(j') H[j'], c(j) = j / nb the count of table entry j
+struct CatTerm {
+    const unsigned* H; int nb;
+    __device__ unsigned long long operator()(unsigned long long j) const { return (unsigned long long)(j / (unsigned)nb) * H[j]; }
+};
 
 // Emit: workgroup b walks its tile 256 voxels at a time, in order.  A voxel of count c >= 1 is the r-th voxel of that count in
 // this step, so its halos start at S[c nb + b] + c r (S is this workgroup's cursor of count c: advanced by c per voxel, by the
@@ -319,27 +248,18 @@ __global__ __launch_bounds__(256) void k_paint_wsum(const double* w, unsigned lo
     acc = block_reduce(acc, 0);
     if (threadIdx.x == 0) partials[blockIdx.x] = acc;
 }
-__device__ __forceinline__ int paint_exponent(double wsum) {
-    int e = 0;
-    if (wsum > 0.0) (void)frexp(wsum, &e);        // wsum < 2^e
-    return 61 - e;
-}
-__device__ __forceinline__ long long wrap(long long m, int N) {
-    m %= N;
-    return m < 0 ? m + N : m;
-}
 // nodes and weights of one axis: window 0 ngp, 1 cic, 2 tsc
 __device__ __forceinline__ int axis_weights(double u, int window, int N, long long (&m)[3], double (&w)[3]) {
     if (window == 1) {
         const double f0 = floor(u), f = u - f0;
-        m[0] = wrap((long long)f0, N); m[1] = wrap((long long)f0 + 1, N);
+        m[0] = wrap_node((long long)f0, N); m[1] = wrap_node((long long)f0 + 1, N);
         w[0] = 1.0 - f; w[1] = f;
         return 2;
     }
     const double c = floor(u + 0.5);
-    if (window == 0) { m[0] = wrap((long long)c, N); w[0] = 1.0; return 1; }
+    if (window == 0) { m[0] = wrap_node((long long)c, N); w[0] = 1.0; return 1; }
     const double d = u - c, a = 0.5 - d, b = 0.5 + d;
-    m[0] = wrap((long long)c - 1, N); m[1] = wrap((long long)c, N); m[2] = wrap((long long)c + 1, N);
+    m[0] = wrap_node((long long)c - 1, N); m[1] = wrap_node((long long)c, N); m[2] = wrap_node((long long)c + 1, N);
     w[0] = 0.5 * (a * a); w[1] = 0.75 - d * d; w[2] = 0.5 * (b * b);
     return 3;
 }
@@ -347,7 +267,7 @@ template <bool TWO>
 __global__ __launch_bounds__(256) void k_paint(const double* pos, const double* wt, unsigned long long n, int window, int N,
                                                double s0, double s1, double s2, const double* wsum,
                                                unsigned long long* acc_hi, unsigned long long* acc_lo) {
-    const int F = paint_exponent(wsum[0]) + (TWO ? 32 : 0);
+    const int F = fx_exponent(wsum[0], 61) + (TWO ? 32 : 0);
     const double scale = ldexp(1.0, F);
     for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
         const double x0 = pos[3 * i], x1 = pos[3 * i + 1], x2 = pos[3 * i + 2];
@@ -365,10 +285,10 @@ __global__ __launch_bounds__(256) void k_paint(const double* pos, const double* 
                 for (int c = 0; c < n2; ++c) {
                     const double v = (wab * w2[c]) * scale;
                     if (TWO) {
-                        const double hi = floor(v * 2.3283064365386963e-10);
-                        const double lo = v - hi * 4294967296.0;
-                        atomicAdd(&acc_hi[row + m2[c]], (unsigned long long)(long long)hi);
-                        atomicAdd(&acc_lo[row + m2[c]], (unsigned long long)__double2ll_rn(lo));
+                        unsigned long long hi, lo;
+                        fx_split(v, hi, lo);
+                        atomicAdd(&acc_hi[row + m2[c]], hi);
+                        atomicAdd(&acc_lo[row + m2[c]], lo);
                     } else {
                         atomicAdd(&acc_hi[row + m2[c]], (unsigned long long)__double2ll_rn(v));
                     }
@@ -379,11 +299,9 @@ __global__ __launch_bounds__(256) void k_paint(const double* pos, const double* 
 template <typename T, bool TWO>
 __global__ __launch_bounds__(256) void k_paint_finish(const unsigned long long* acc_hi, const unsigned long long* acc_lo,
                                                       unsigned long long n, const double* wsum, T* out) {
-    const int F = paint_exponent(wsum[0]) + (TWO ? 32 : 0);
+    const int F = fx_exponent(wsum[0], 61) + (TWO ? 32 : 0);
     for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
-        double v = (double)(long long)acc_hi[i];
-        if (TWO) v = v * 4294967296.0 + (double)acc_lo[i];
-        out[i] = (T)ldexp(v, -F);
+        out[i] = (T)(TWO ? fx_join(acc_hi[i], acc_lo[i], F) : ldexp((double)(long long)acc_hi[i], -F));
     }
 }
 
@@ -396,7 +314,7 @@ __global__ __launch_bounds__(256) void k_paint_compensate(T* half, int N, int NR
         const unsigned long long row = q / (unsigned)NZP;
         const int l = (int)(q - row * (unsigned)NZP), j = (int)(row % (unsigned)NR), i = (int)(row / (unsigned)NR);
         if (l >= NZV || j >= N) continue;
-        const int ms[3] = {i <= N / 2 ? i : i - N, j <= N / 2 ? j : j - N, l};
+        const int ms[3] = {i <= N / 2 ? i : i - N, j <= N / 2 ? j : j - N, l};     // (N/2 stays +N/2: not mode_of; sinc is even)
         double f = 1.0;
         for (int a = 0; a < 3; ++a) {
             if (!ms[a]) continue;
@@ -411,17 +329,6 @@ __global__ __launch_bounds__(256) void k_paint_compensate(T* half, int N, int NR
     }
 }
 
-int grid_for(unsigned long long n, const fb_plan* p) {
-    const unsigned long long b = (n + 255) / 256, cap = 8ull * p->num_cu * 8;
-    return (int)std::max(1ull, std::min(b, cap));
-}
-int ensure(void** buf, size_t* cap, size_t bytes) {
-    if (bytes <= *cap) return FB_OK;
-    if (*buf) { FB_HIP(hipFree(*buf)); *buf = nullptr; *cap = 0; }
-    FB_HIP(hipMalloc(buf, bytes));
-    *cap = bytes;
-    return FB_OK;
-}
 int ensure_small(fb_plan* p) {
     if (!p->halo_small) FB_HIP(hipMalloc(&p->halo_small, FB_HALO_SMALL));
     return FB_OK;
@@ -502,10 +409,9 @@ int cat_emit(fb_plan* p, const void* counts, int64_t kmax, const double* U, int 
     while ((n + tile - 1) / tile * K > FB_HALO_TABLE_MAX && tile < n) tile *= 2;
     const int nb = (int)((n + tile - 1) / tile);
     const unsigned long long M = K * nb;
-    const int nc = (int)((M + FB_SCAN_CH - 1) / FB_SCAN_CH);
-    // work: H [M] u32 | S [M] u64 | csum [nc + 1] u64
-    const size_t offS = (M * 4 + 15) / 16 * 16, offC = offS + M * 8;
-    int r = ensure(&p->halo_work, &p->halo_work_cap, offC + ((size_t)nc + 1) * 8);
+    // work: H [M] u32 | S [M + 1] u64 (S[M]: the total, not read) | csum [chunks] u64
+    const size_t offS = (M * 4 + 15) / 16 * 16, offC = offS + (M + 1) * 8;
+    int r = ensure_bytes(&p->halo_work, &p->halo_work_cap, offC + (size_t)scan_chunks(M) * 8);
     if (r) return r;
     unsigned* H = (unsigned*)p->halo_work;
     unsigned long long* S = (unsigned long long*)((char*)p->halo_work + offS);
@@ -514,12 +420,8 @@ int cat_emit(fb_plan* p, const void* counts, int64_t kmax, const double* U, int 
     { FbProfScope _ps(p, FBK_REALOP, s);
     hipLaunchKernelGGL((k_cat_hist<T>), dim3(nb), dim3(256), 0, s, (const T*)counts, n, tile, nb, (int)kmax, H); }
     FB_LAUNCH_CHECK("k_cat_hist");
-    hipLaunchKernelGGL(k_scan_chunks, dim3(nc), dim3(256), 0, s, (const unsigned*)H, M, nb, csum);
-    FB_LAUNCH_CHECK("k_scan_chunks");
-    hipLaunchKernelGGL(k_scan_top, dim3(1), dim3(256), 0, s, csum, nc);
-    FB_LAUNCH_CHECK("k_scan_top");
-    hipLaunchKernelGGL(k_scan_apply, dim3(nc), dim3(256), 0, s, (const unsigned*)H, M, nb, (const unsigned long long*)csum, S);
-    FB_LAUNCH_CHECK("k_scan_apply");
+    r = exscan(CatTerm{H, nb}, M, csum, S, s);
+    if (r) return r;
     { FbProfScope _ps(p, FBK_REALOP, s);
     hipLaunchKernelGGL((k_cat_emit<T>), dim3(nb), dim3(256), 0, s, (const T*)counts, n, tile, nb, p->N, S, U, scatter,
                        rng_key(seed, real), p->L[0] / (double)p->N, p->L[1] / (double)p->N, p->L[2] / (double)p->N, pos); }
@@ -532,7 +434,7 @@ int paint(fb_plan* p, const double* pos, const double* wt, unsigned long long n,
     const unsigned long long nv = (unsigned long long)p->N * p->N * p->N;
     constexpr bool TWO = sizeof(T) == 8;
     int r = ensure_small(p);
-    if (!r) r = ensure(&p->halo_acc, &p->halo_acc_cap, nv * 8 * (TWO ? 2 : 1));
+    if (!r) r = ensure_bytes(&p->halo_acc, &p->halo_acc_cap, nv * 8 * (TWO ? 2 : 1));
     if (r) return r;
     double* part = (double*)p->halo_small;
     double* wsum = part + FB_HALO_RED_BLOCKS;

@@ -9,6 +9,7 @@
 #include "../../include/fastbox_hip.h"
 #include "fb_plan.h"
 #include "fb_api_util.h"
+#include "fb_dev.h"
 #include "fb_rng.h"
 #include <cmath>
 
@@ -18,16 +19,11 @@
 #define FB_GCR_STREAM_OMEGA3 9u
 
 namespace {
+using namespace fb;
 
 typedef double fb_d4 __attribute__((ext_vector_type(4)));
 typedef double fb_d2 __attribute__((ext_vector_type(2)));
 typedef float fb_f4 __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ double wsum(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 // four consecutive elements, 16-byte aligned where T is float and 32-byte aligned (read as two halves) where it is double
 __device__ __forceinline__ void load4(const double* __restrict__ src, double (&v)[4]) {
@@ -223,7 +219,7 @@ __global__ __launch_bounds__(256) void k_cg_init(const double* __restrict__ b, d
         x[p * N + c] = 0.0; r[p * N + c] = v;
         s += v * v;
     }
-    s = wsum(s);
+    s = wave_sum(s);
     if (lane == 0) {
         const int on = s > 0.0 ? 1 : 0;             // (a NaN in b leaves the row off; the final residual reports it)
         st.bb[p] = s; st.rz[p] = 0.0; st.active[p] = on; st.n_iter[p] = 0;
@@ -239,7 +235,7 @@ __global__ __launch_bounds__(256) void k_cg_step(const double* __restrict__ pd, 
     if (p >= npix || !st.active[p]) return;
     double s = 0.0;
     for (int c = lane; c < N; c += 64) s += pd[p * N + c] * ap[p * N + c];
-    s = wsum(s);
+    s = wave_sum(s);
     const double rz = st.rz[p];
     const double alpha = (s != 0.0 && s == s) ? rz / s : 0.0;          // 0 / 0 selects 0
     double rr = 0.0;
@@ -250,7 +246,7 @@ __global__ __launch_bounds__(256) void k_cg_step(const double* __restrict__ pd, 
         r[i] = v;
         rr += v * v;
     }
-    rr = wsum(rr);
+    rr = wave_sum(rr);
     if (lane == 0) {
         st.n_iter[p] += 1;
         if (rr <= tol2 * st.bb[p] || alpha == 0.0) st.active[p] = 0;   // alpha = 0: no progress is possible any more
@@ -266,7 +262,7 @@ __global__ __launch_bounds__(256) void k_cg_direction(const double* __restrict__
     if (p >= npix || !st.active[p]) return;
     double s = 0.0;
     for (int c = lane; c < N; c += 64) s += r[p * N + c] * z[p * N + c];
-    s = wsum(s);
+    s = wave_sum(s);
     const double old = st.rz[p];
     const double beta = (first || old == 0.0) ? 0.0 : s / old;
     for (int c = lane; c < N; c += 64) {
@@ -284,7 +280,7 @@ __global__ __launch_bounds__(256) void k_row_residual(const double* __restrict__
     if (p >= npix) return;
     double s = 0.0;
     for (int c = lane; c < N; c += 64) { const double v = b[p * N + c] - ax[p * N + c]; s += v * v; }
-    s = wsum(s);
+    s = wave_sum(s);
     if (lane == 0) {
         const double bb = st.bb[p];
         res[p] = bb > 0.0 ? sqrt(s / bb) : (bb == 0.0 ? 0.0 : NAN);

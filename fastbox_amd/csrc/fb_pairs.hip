@@ -185,7 +185,7 @@ PairWork pair_layout(unsigned long long n1, unsigned long long n2, unsigned long
         w.cat[q].cursor = o; o += align16((size_t)ncells * 4);
         w.cat[q].cellid = o; o += align16((size_t)n[q] * 4);
     }
-    w.csum = o; o += align16((size_t)scan_chunks(ncells + 1) * 4);
+    w.csum = o; o += align16((size_t)scan_chunks(ncells) * 4);
     w.items = o; o += align16((size_t)(n1 / FB_FOF_TILE + 1) * 8);
     w.total = o;
     return w;
@@ -269,17 +269,12 @@ int fb_pair_count(fb_plan* p, const double* pos1, int64_t n1, const double* pos2
     FB_HIP(hipStreamSynchronize(s));                                  // (the edges have been read by now, too)
     if (h.err & FB_FOF_ERR_POS) { *bad = 1; return FB_OK; }
     if (n1 == 0 || (!autoc && n2 == 0)) return FB_OK;                 // no pair: the counts are zero
-    const int nch = (int)scan_chunks(ncells + 1);
     for (int q = 0; q < ncat; ++q) {
         unsigned *start = (unsigned*)(wb + w.cat[q].start), *cursor = (unsigned*)(wb + w.cat[q].cursor),
                  *cellid = (unsigned*)(wb + w.cat[q].cellid);
         double* spos = (double*)(wb + w.cat[q].spos);
-        hipLaunchKernelGGL(k_fof_scan_chunks, dim3(nch), dim3(256), 0, s, (const unsigned*)cursor, ncells, csum);
-        FB_LAUNCH_CHECK("k_fof_scan_chunks");
-        hipLaunchKernelGGL(k_fof_scan_top, dim3(1), dim3(256), 0, s, csum, nch);
-        FB_LAUNCH_CHECK("k_fof_scan_top");
-        hipLaunchKernelGGL(k_fof_scan_apply, dim3(nch), dim3(256), 0, s, (const unsigned*)cursor, ncells, (const unsigned*)csum, start);
-        FB_LAUNCH_CHECK("k_fof_scan_apply");
+        const int rs = exscan(ScanPlain{cursor}, ncells, csum, start, s);       // start[ncells] = n[q]
+        if (rs) return rs;
         FB_HIP(hipMemsetAsync(cursor, 0, (size_t)ncells * 4, s));
         hipLaunchKernelGGL(k_fof_scatter, dim3(grid_for(n[q], p)), dim3(256), 0, s, pos[q], n[q], g, (const unsigned*)cellid,
                            (const unsigned*)start, cursor, (unsigned*)nullptr, spos, (unsigned*)nullptr);

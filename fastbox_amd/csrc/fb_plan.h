@@ -65,7 +65,7 @@ struct fb_plan {
     int prow = 0;
     double* scratch = nullptr;   // small reduction scratch [FB_SCRATCH]
     double* bin_partials = nullptr;   // fused binning: [workgroups][2*nbins]
-    size_t bin_partials_cap = 0;
+    size_t bin_partials_cap = 0;      // bytes, like every *_cap below: the buffers grow through ensure_bytes
     long long bin_rows = 0;
     long long bin_rows_main = 0;      // of which the fused binning pass itself wrote (the rest: k_bin_packed_plane)
     long long bin_append_cap = 0;     // > 0: binning launches append their columns to a shared table of this many (k_z chunks)
@@ -80,14 +80,14 @@ struct fb_plan {
     double* sep_edges = nullptr;      // [FB_MAX_SEP_BINS + 1]
     std::vector<std::vector<double>> sep_geom;
     double* sep_partials = nullptr;   // [nv nbins][workgroups] of k_sep_bin (grown on demand: up to 3 x 1024 values per workgroup)
-    size_t sep_partials_cap = 0;      // doubles
+    size_t sep_partials_cap = 0;
 
     // power spectrum in (k, mu) bins (fb_power.hip): the bin table on the device, per-workgroup partials, and the
     // data-independent sums (modes, sum |k|, sum mu per cell) per (edges, nmu) already computed -- [edges..., nmu, modes...,
     // sum |k|..., sum mu...] per entry, most recent last
     double* pk_tab = nullptr;         // [FB_PK_MAX_K + FB_PK_MAX_MU + 2]
     double* pk_partials = nullptr;    // [values][workgroups] of k_pk_bin (grown on demand)
-    size_t pk_partials_cap = 0;       // doubles
+    size_t pk_partials_cap = 0;
     std::vector<std::vector<double>> pk_geom;
 
     // halo tracers (fb_halo.hip): reduction partials, the catalogue's (count, block) tables, the painting accumulators
@@ -149,7 +149,8 @@ void fb_set_error(const std::string& msg);
 int fb_hip_check(hipError_t e, const char* what);
 #define FB_HIP(x) do { int _r = fb_hip_check((x), #x); if (_r) return _r; } while (0)
 #define FB_LAUNCH_CHECK(name) do { int _r = fb_hip_check(hipGetLastError(), name); if (_r) return _r; } while (0)
-// grow-only device work buffer (the plan's pca_work and its like): the one policy for everything that shares such a buffer
+// grow-only device work buffer (the plan's pca_work and its like): the one policy for every buffer of the plan that grows on
+// demand; *cap is in bytes
 static inline int ensure_bytes(void** buf, size_t* cap, size_t need) {
     if (*cap >= need) return FB_OK;
     if (*buf) FB_HIP(hipFree(*buf));

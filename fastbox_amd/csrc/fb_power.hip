@@ -4,7 +4,8 @@
 #include "../../include/fastbox_hip.h"
 #include "fb_plan.h"
 #include "fb_api_util.h"
-#include "fb_field_kernels.h"
+#include "fb_dev.h"                      // mode_of, wave_sum, k_bin_finish
+#include "fb_fft.h"                      // cx<T>
 #include "fb_kshell.h"
 #include <algorithm>
 #include <cmath>
@@ -30,15 +31,6 @@ struct PkArgs {
 
 #define FB_PK_WAVES 4      // waves per workgroup when the per-wave rows fit (fewer otherwise: pk_waves)
 #define FB_PK_GROUP 4      // 64-lane steps whose loads a wave issues together (a row of N <= 512 is two groups)
-
-__device__ __forceinline__ double pk_sq2(double a, double b) {
-#pragma clang fp contract(off)
-    return a * a + b * b;
-}
-__device__ __forceinline__ double pk_add_sq(double s, double c) {
-#pragma clang fp contract(off)
-    return s + c * c;
-}
 
 // -1 below the first edge, nk at or beyond the last one
 __device__ __forceinline__ int pk_kbin(const double* T, const PkArgs& a, double k2) {
@@ -93,7 +85,7 @@ void k_pk_bin(const cx<T>* __restrict__ h1, const cx<T>* __restrict__ h2, double
     const long long nrows = (long long)N * N;
     for (long long row = (long long)blockIdx.x * waves + wave; row < nrows; row += (long long)gridDim.x * waves) {
         const int i = (int)(row / N), j = (int)(row % N);
-        const double kperp2 = pk_sq2((double)mode_of(i, N) * a.kf[0], (double)mode_of(j, N) * a.kf[1]);
+        const double kperp2 = sq2((double)mode_of(i, N) * a.kf[0], (double)mode_of(j, N) * a.kf[1]);
         if (kperp2 >= tlast) continue;                               // the whole row lies beyond the last edge
         const long long base = ((long long)i * a.NR + j) * a.NZP;
         bool done = false;
@@ -112,7 +104,7 @@ void k_pk_bin(const cx<T>* __restrict__ h1, const cx<T>* __restrict__ h2, double
                 const int l0 = g0 + 64 * c, l = l0 + lane;
                 if (l0 >= a.NZV) { done = true; break; }
                 const double kz = (double)l * a.kf[2];               // l <= N / 2: the stored k_z are the non-negative ones
-                const double k2 = pk_add_sq(kperp2, kz);
+                const double k2 = add_sq(kperp2, kz);
                 if (__shfl(k2, 0, 64) >= tlast) { done = true; break; }   // lane 0 beyond the last edge: so is the rest
                 const bool in = l < a.NZV && k2 > 0.0;
                 int key = 0x7fffffff;
@@ -201,12 +193,8 @@ int pk_launch(fb_plan* p, bool geom, int which, const void* h1, const void* h2, 
     const long long resident = std::max(1LL, std::min(8LL, (long long)((160 * 1024) / lds)));   // workgroups per CU
     long long blocks = std::min((rows + waves - 1) / waves, resident * p->num_cu);
     if (blocks < 1) blocks = 1;
-    const size_t need = (size_t)blocks * a.nv * nc;
-    if (need > p->pk_partials_cap) {
-        if (p->pk_partials) { FB_HIP(hipFree(p->pk_partials)); p->pk_partials = nullptr; p->pk_partials_cap = 0; }
-        FB_HIP(hipMalloc((void**)&p->pk_partials, need * sizeof(double)));
-        p->pk_partials_cap = need;
-    }
+    const int rb = ensure_bytes((void**)&p->pk_partials, &p->pk_partials_cap, (size_t)blocks * a.nv * nc * sizeof(double));
+    if (rb) return rb;
     const void* fn = geom ? PkKernels<T>::geom() : PkKernels<T>::data();
     if (lds > 65536) FB_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     { FbProfScope _ps(p, FBK_BIN, s);
@@ -218,7 +206,7 @@ int pk_launch(fb_plan* p, bool geom, int which, const void* h1, const void* h2, 
                            (const cx<T>*)h2, p->pk_partials, a); }
     FB_LAUNCH_CHECK("k_pk_bin");
     { FbProfScope _ps(p, FBK_BIN, s);
-    hipLaunchKernelGGL(k_bin_finish, dim3(a.nv * nc), dim3(256), 0, s, p->pk_partials, (int)blocks, a.nv * nc, out_dev); }
+    hipLaunchKernelGGL(k_bin_finish<>, dim3(a.nv * nc), dim3(256), 0, s, p->pk_partials, (int)blocks, a.nv * nc, out_dev); }
     FB_LAUNCH_CHECK("k_bin_finish");
     return FB_OK;
 }
@@ -228,10 +216,7 @@ int pk_check(const double* kedges, int nk, int nmu, int lmax) {
     FB_REQUIRE(nmu >= 1 && nmu <= FB_PK_MAX_MU, "nmu must be in 1..128");
     FB_REQUIRE(lmax == 0 || lmax == 2 || lmax == 4, "lmax must be 0, 2 or 4");
     FB_REQUIRE((long long)nk * nmu * (lmax / 2 + 1) <= FB_PK_MAX_VALUES, "nk * nmu * (lmax / 2 + 1) must be <= 5120");
-    FB_REQUIRE(kedges[0] >= 0.0, "the first k edge must be >= 0");
-    for (int q = 0; q < nk; ++q) FB_REQUIRE(std::isfinite(kedges[q]), "k edges must be finite (the last may be inf)");
-    for (int q = 1; q <= nk; ++q) FB_REQUIRE(kedges[q] > kedges[q - 1], "k edges must be strictly ascending");
-    return FB_OK;
+    return kshell_check_edges(kedges, nk);
 }
 
 int bin_power_kmu(fb_plan* p, const void* half1, const void* half2, const double* kedges, int nk, int nmu, int lmax,
@@ -248,7 +233,7 @@ int bin_power_kmu(fb_plan* p, const void* half1, const void* half2, const double
     PkArgs a;
     a.tab = p->pk_tab; a.N = p->N; a.NZV = p->NZV; a.NZP = p->NZP; a.NR = p->NR;
     a.nk = nk; a.nmu = nmu; a.nv = nl; a.which = 0;
-    for (int q = 0; q < 3; ++q) a.kf[q] = 6.283185307179586 / p->L[q];   // 2 * np.pi / L_a
+    fill_kf(p, a.kf);
     const double dk = (kedges[nk] - kedges[0]) / nk;
     bool uni = std::isfinite(dk) && dk > 0.0;
     for (int q = 0; uni && q <= nk; ++q) uni = std::fabs(kedges[q] - (kedges[0] + q * dk)) <= 1e-6 * dk;

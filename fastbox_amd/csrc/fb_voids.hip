@@ -8,6 +8,8 @@
 #include "../../include/fastbox_hip.h"
 #include "fb_plan.h"
 #include "fb_api_util.h"
+#include "fb_dev.h"
+#include "fb_scan.h"
 #include <algorithm>
 #include <cmath>
 
@@ -24,6 +26,7 @@
 #define FB_VOID_STACK_CHUNKS 64          // void chunks of the stacking partials
 
 namespace {
+using namespace fb;
 
 __device__ __forceinline__ bool in_mask(int kind, double thr, const void* mp, double v, unsigned long long g, int prec) {
     if (!isfinite(v)) return false;
@@ -96,22 +99,6 @@ __global__ __launch_bounds__(256) void k_ws_jump(unsigned* par, unsigned long lo
 }
 
 // exclusive scan of v over the workgroup's 256 lanes in LDS (Hillis-Steele); `total` receives the sum
-__device__ unsigned block_exscan_u32(unsigned v, unsigned* total) {
-    __shared__ unsigned sh[256];
-    sh[threadIdx.x] = v;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {
-        const unsigned a = threadIdx.x >= (unsigned)o ? sh[threadIdx.x - o] : 0u;
-        __syncthreads();
-        sh[threadIdx.x] += a;
-        __syncthreads();
-    }
-    const unsigned incl = sh[threadIdx.x];
-    *total = sh[255];
-    __syncthreads();
-    return incl - v;
-}
-
 // minima (par[i] == i) per tile of FB_VOID_TILE voxels
 __global__ __launch_bounds__(256) void k_ws_count(const unsigned* par, unsigned long long n, unsigned* cnt) {
     const unsigned long long b0 = (unsigned long long)blockIdx.x * FB_VOID_TILE;
@@ -121,7 +108,7 @@ __global__ __launch_bounds__(256) void k_ws_count(const unsigned* par, unsigned 
         if (i < n && par[i] == (unsigned)i) ++c;
     }
     unsigned tot;
-    (void)block_exscan_u32(c, &tot);
+    (void)block_exscan(c, &tot);
     if (threadIdx.x == 0) cnt[blockIdx.x] = tot;
 }
 
@@ -133,7 +120,7 @@ __global__ __launch_bounds__(256) void k_ws_roots(unsigned* par, unsigned long l
         const unsigned long long i = b0 + s0 + threadIdx.x;
         const unsigned isr = (i < n && par[i] == (unsigned)i) ? 1u : 0u;
         unsigned tot;
-        const unsigned ex = block_exscan_u32(isr, &tot);
+        const unsigned ex = block_exscan(isr, &tot);
         if (isr) par[i] = FB_VOID_ROOT | (run + ex + 1u);
         run += tot;
     }
@@ -152,77 +139,24 @@ __global__ __launch_bounds__(256) void k_ws_label(unsigned* par, unsigned long l
     }
 }
 
-// ---- exclusive scan of u32 values (totals below 2^31): chunk sums, one workgroup over the chunk sums, the chunks ---------
-#define FB_VSCAN_PER 16
-#define FB_VSCAN_CH (256 * FB_VSCAN_PER)
-__global__ __launch_bounds__(256) void k_vscan_chunks(const unsigned* in, unsigned long long n, unsigned* csum) {
-    const unsigned long long j0 = (unsigned long long)blockIdx.x * FB_VSCAN_CH;
-    unsigned s = 0;
-    for (int q = 0; q < FB_VSCAN_PER; ++q) {
-        const unsigned long long j = j0 + (unsigned long long)q * 256 + threadIdx.x;
-        s += j < n ? in[j] : 0u;
-    }
-    unsigned tot;
-    (void)block_exscan_u32(s, &tot);
-    if (threadIdx.x == 0) csum[blockIdx.x] = tot;
-}
-__global__ __launch_bounds__(256) void k_vscan_top(unsigned* csum, int nc) {
-    unsigned carry = 0;
-    for (int base = 0; base < nc; base += 256) {
-        const int i = base + threadIdx.x;
-        const unsigned v = i < nc ? csum[i] : 0u;
-        unsigned tot;
-        const unsigned ex = block_exscan_u32(v, &tot);
-        if (i < nc) csum[i] = carry + ex;
-        carry += tot;
-    }
-    if (threadIdx.x == 0) csum[nc] = carry;
-}
-__global__ __launch_bounds__(256) void k_vscan_apply(const unsigned* in, unsigned long long n, const unsigned* csum, unsigned* out) {
-    const unsigned long long j0 = (unsigned long long)blockIdx.x * FB_VSCAN_CH + (unsigned long long)threadIdx.x * FB_VSCAN_PER;
-    unsigned w[FB_VSCAN_PER], s = 0;
-    for (int q = 0; q < FB_VSCAN_PER; ++q) { w[q] = j0 + q < n ? in[j0 + q] : 0u; s += w[q]; }
-    unsigned tot;
-    unsigned run = csum[blockIdx.x] + block_exscan_u32(s, &tot);
-    for (int q = 0; q < FB_VSCAN_PER; ++q) {
-        if (j0 + q < n) out[j0 + q] = run;
-        run += w[q];
-    }
-}
-
 // ---- region statistics ----------------------------------------------------------------------------------------------------
 // Accumulators acc (u64) [16][n1]: 0 count, 1-3 sums of the voxel indices per axis, 4 least key of f, 5 least voxel index of that
 // key, 6-15 five fixed-point (hi, lo) pairs: sum f, sum w, sum w ix, sum w iy, sum w iz (w = max(-f, 0)).
-__device__ __forceinline__ double wave_sum(double v) {
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
 // order-preserving key of a finite double (-0 is +0)
 __device__ __forceinline__ unsigned long long okey(double v) {
     if (v == 0.0) v = 0.0;
     const unsigned long long b = (unsigned long long)__double_as_longlong(v);
     return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
 }
-// fixed-point scale exponent for a bound B (every |sum| < 2^e): values are scaled by 2^(93 - e), about 94 significant bits
-__device__ __forceinline__ int fx_exp(double B) {
-    int e = 0;
-    if (B > 0.0) (void)frexp(B, &e);
-    return 93 - e;
-}
-// v = x 2^F split into hi = floor(v 2^-32) (int64) and lo = v - hi 2^32 in [0, 2^32]: integer adds, exact and order-free
-__device__ __forceinline__ void fx_split(double x, double scale, unsigned long long& hi, unsigned long long& lo) {
-    const double v = x * scale;
-    const double h = floor(v * 2.3283064365386963e-10);
-    hi = (unsigned long long)(long long)h;
-    lo = (unsigned long long)__double2ll_rn(v - h * 4294967296.0);
-}
+// fixed point in two 64-bit accumulators (fb_dev.h): for a bound B (every |sum| < 2^e) values are scaled by 2^(93 - e)
 __device__ __forceinline__ void fx_add(unsigned long long* hi, unsigned long long* lo, double x, double scale) {
     if (x == 0.0) return;
     unsigned long long h, l;
-    fx_split(x, scale, h, l);
+    fx_split(x * scale, h, l);
     atomicAdd(hi, h);
     atomicAdd(lo, l);
 }
+// (not fx_join: the low words are summed unsigned here and their carry, lo >> 32, moves into hi first)
 __device__ __forceinline__ double fx_value(unsigned long long hi, unsigned long long lo, int F) {
     const long long h = (long long)hi + (long long)(lo >> 32);
     return ldexp((double)h * 4294967296.0 + (double)(lo & 0xFFFFFFFFull), -F);
@@ -275,7 +209,7 @@ template <typename T>
 __global__ __launch_bounds__(256) void k_rs_accum(const int* lab, const T* f, unsigned long long n, int N, unsigned long long n1,
                                                   const double* bound, unsigned long long* acc) {
     const double B = f ? bound[0] : 0.0;
-    const double s1 = ldexp(1.0, fx_exp(B)), s2 = ldexp(1.0, fx_exp(B * (double)N));
+    const double s1 = ldexp(1.0, fx_exponent(B, 93)), s2 = ldexp(1.0, fx_exponent(B * (double)N, 93));
     const int lane = threadIdx.x & 63;
     const unsigned long long NN = (unsigned long long)N * N;
     unsigned long long z[14] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, zkey = ~0ull;    // label 0: count, ix, iy, iz, 5 x (hi, lo)
@@ -319,7 +253,7 @@ __global__ __launch_bounds__(256) void k_rs_accum(const int* lab, const T* f, un
             const double xs[5] = {vf, vw, wx, wy, wz};
             for (int q = 0; q < 5; ++q) {
                 unsigned long long h, lo;
-                fx_split(xs[q], q < 2 ? s1 : s2, h, lo);
+                fx_split(xs[q] * (q < 2 ? s1 : s2), h, lo);
                 z[4 + 2 * q] += h; z[5 + 2 * q] += lo;
             }
         } else if (tail && l > 0 && (unsigned long long)l < n1) {
@@ -365,7 +299,7 @@ __global__ __launch_bounds__(256) void k_rs_finish(const unsigned long long* acc
     long long* oi = (long long*)out;
     double* od = (double*)out;
     const double B = has_field ? bound[0] : 0.0;
-    const int F1 = fx_exp(B), F2 = fx_exp(B * (double)N);
+    const int F1 = fx_exponent(B, 93), F2 = fx_exponent(B * (double)N, 93);
     for (unsigned long long l = (unsigned long long)blockIdx.x * 256 + threadIdx.x; l < n1; l += (unsigned long long)gridDim.x * 256) {
         const unsigned long long cnt = acc[l];
         oi[l] = (long long)cnt;
@@ -497,21 +431,11 @@ __global__ __launch_bounds__(256) void k_stack_finish(const double* psum, const 
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
-int grid_for(unsigned long long n, const fb_plan* p) {
-    const unsigned long long b = (n + 255) / 256, cap = 8ull * p->num_cu * 8;
-    return (int)std::max(1ull, std::min(b, cap));
-}
 int ensure_small(fb_plan* p) {
     if (!p->void_small) FB_HIP(hipMalloc(&p->void_small, FB_VOID_SMALL));
     return FB_OK;
 }
-int ensure_work(fb_plan* p, size_t bytes) {
-    if (bytes <= p->void_work_cap) return FB_OK;
-    if (p->void_work) { FB_HIP(hipFree(p->void_work)); p->void_work = nullptr; p->void_work_cap = 0; }
-    FB_HIP(hipMalloc(&p->void_work, bytes));
-    p->void_work_cap = bytes;
-    return FB_OK;
-}
+int ensure_work(fb_plan* p, size_t bytes) { return ensure_bytes(&p->void_work, &p->void_work_cap, bytes); }
 unsigned* small_flag(fb_plan* p) { return (unsigned*)p->void_small; }
 unsigned* small_err(fb_plan* p) { return (unsigned*)p->void_small + 1; }
 double* small_bound(fb_plan* p) { return (double*)p->void_small + 1; }
@@ -521,18 +445,6 @@ int read_u32(const unsigned* dev, unsigned* host, hipStream_t s) {
     FB_HIP(hipStreamSynchronize(s));
     return FB_OK;
 }
-unsigned long long vscan_chunks(unsigned long long n) { return (n + FB_VSCAN_CH - 1) / FB_VSCAN_CH; }
-// exclusive scan of in[0..n) into out; csum: [chunks + 1] u32, csum[chunks] = the total
-int vscan(const unsigned* in, unsigned long long n, unsigned* out, unsigned* csum, hipStream_t s) {
-    const int nc = (int)vscan_chunks(n);
-    hipLaunchKernelGGL(k_vscan_chunks, dim3(nc), dim3(256), 0, s, in, n, csum);
-    FB_LAUNCH_CHECK("k_vscan_chunks");
-    hipLaunchKernelGGL(k_vscan_top, dim3(1), dim3(256), 0, s, csum, nc);
-    FB_LAUNCH_CHECK("k_vscan_top");
-    hipLaunchKernelGGL(k_vscan_apply, dim3(nc), dim3(256), 0, s, in, n, (const unsigned*)csum, out);
-    FB_LAUNCH_CHECK("k_vscan_apply");
-    return FB_OK;
-}
 
 template <typename T>
 int watershed(fb_plan* p, const void* field, int kind, double thr, const void* mask, unsigned* par, int64_t* nreg, hipStream_t s) {
@@ -540,11 +452,11 @@ int watershed(fb_plan* p, const void* field, int kind, double thr, const void* m
     const unsigned long long n = (unsigned long long)N * N * N;
     const unsigned long long nb = (n + FB_VOID_TILE - 1) / FB_VOID_TILE;
     int r = ensure_small(p);
-    if (!r) r = ensure_work(p, (size_t)(2 * nb + vscan_chunks(nb) + 1) * 4);
+    if (!r) r = ensure_work(p, (size_t)(2 * nb + 1 + scan_chunks(nb)) * 4);
     if (r) return r;
-    unsigned* cnt = (unsigned*)p->void_work;
-    unsigned* off = cnt + nb;
-    unsigned* csum = off + nb;
+    unsigned* cnt = (unsigned*)p->void_work;             // [nb]
+    unsigned* off = cnt + nb;                            // [nb + 1]: the scan of cnt, off[nb] = the number of minima (totals below 2^31)
+    unsigned* csum = off + nb + 1;
     unsigned* flag = small_flag(p);
     { FbProfScope _ps(p, FBK_REALOP, s);
     hipLaunchKernelGGL((k_ws_descend<T>), dim3((N + WS_TZ - 1) / WS_TZ, (N + WS_TY - 1) / WS_TY, (N + WS_TX - 1) / WS_TX), dim3(256),
@@ -565,14 +477,14 @@ int watershed(fb_plan* p, const void* field, int kind, double thr, const void* m
     }
     hipLaunchKernelGGL(k_ws_count, dim3((unsigned)nb), dim3(256), 0, s, (const unsigned*)par, n, cnt);
     FB_LAUNCH_CHECK("k_ws_count");
-    r = vscan(cnt, nb, off, csum, s);
+    r = exscan(ScanPlain{cnt}, nb, csum, off, s);
     if (r) return r;
     hipLaunchKernelGGL(k_ws_roots, dim3((unsigned)nb), dim3(256), 0, s, par, n, (const unsigned*)off);
     FB_LAUNCH_CHECK("k_ws_roots");
     hipLaunchKernelGGL(k_ws_label, dim3(grid_for(n, p)), dim3(256), 0, s, par, n);
     FB_LAUNCH_CHECK("k_ws_label");
     unsigned tot = 0;
-    r = read_u32(csum + vscan_chunks(nb), &tot, s);
+    r = read_u32(off + nb, &tot, s);
     if (r) return r;
     *nreg = (int64_t)tot;
     return FB_OK;
@@ -615,14 +527,13 @@ int region_stats(fb_plan* p, const int* lab, int64_t nl, const void* field, void
 int merge_regions(fb_plan* p, const int* lab, int64_t nl, const double* mean, double thr, int* out, int64_t* nmerged, hipStream_t s) {
     const int N = p->N;
     const unsigned long long n = (unsigned long long)N * N * N, n1 = (unsigned long long)nl + 1;
-    const unsigned long long nc = vscan_chunks(n1);
     int r = ensure_small(p);
-    if (!r) r = ensure_work(p, (size_t)(3 * n1 + nc + 1) * 4);
+    if (!r) r = ensure_work(p, (size_t)(3 * n1 + 1 + scan_chunks(n1)) * 4);
     if (r) return r;
     unsigned* comp = (unsigned*)p->void_work;
     unsigned* flags = comp + n1;
-    unsigned* rank = flags + n1;
-    unsigned* csum = rank + n1;
+    unsigned* rank = flags + n1;                         // [n1 + 1]: the scan of flags, rank[n1] = the number of merged regions
+    unsigned* csum = rank + n1 + 1;
     unsigned* changed = small_flag(p);
     hipLaunchKernelGGL(k_mg_init, dim3(grid_for(n1, p)), dim3(256), 0, s, comp, n1);
     FB_LAUNCH_CHECK("k_mg_init");
@@ -654,14 +565,14 @@ int merge_regions(fb_plan* p, const int* lab, int64_t nl, const double* mean, do
     }
     hipLaunchKernelGGL(k_mg_isroot, dim3(grid_for(n1, p)), dim3(256), 0, s, (const unsigned*)comp, n1, flags);
     FB_LAUNCH_CHECK("k_mg_isroot");
-    r = vscan(flags, n1, rank, csum, s);
+    r = exscan(ScanPlain{flags}, n1, csum, rank, s);
     if (r) return r;
     hipLaunchKernelGGL(k_mg_newlab, dim3(grid_for(n1, p)), dim3(256), 0, s, (const unsigned*)comp, (const unsigned*)rank, n1, flags);
     FB_LAUNCH_CHECK("k_mg_newlab");
     hipLaunchKernelGGL(k_mg_relabel, dim3(grid_for(n, p)), dim3(256), 0, s, lab, n, n1, (const unsigned*)flags, out);
     FB_LAUNCH_CHECK("k_mg_relabel");
     unsigned tot = 0;
-    r = read_u32(csum + nc, &tot, s);
+    r = read_u32(rank + n1, &tot, s);
     if (r) return r;
     *nmerged = (int64_t)tot;
     return FB_OK;

@@ -92,6 +92,26 @@ def case_f_tiny(n):
     return _case("F n=%d" % n, np.full((n, 3), 3.), 32., 0.5, 2, vel=None, random=False)
 
 
+# ---- G: a cell grid whose scan carries a running sum across rounds ----------------------------------------------------------
+G_CELLS = (128, 128, 64)                   # 2^20 cells: the scan's 2^20 + 1 outputs are 257 chunks of 4096, one more than a round
+
+
+@functools.lru_cache(maxsize=None)
+def case_g_many_cells():
+    """(pos, L, ell, roots) for the raw link call on G_CELLS cells of the unit box (find_halos never picks so fine a grid for
+    so few particles): a linked pair in cell 0, one in the last cell, one across the periodic corner between those two cells,
+    294 scattered singles.  roots: the definition's."""
+    ell = (1. - 2. ** -20) / 128.
+    pairs = np.array([[0.004, 0.004, 0.012], [0.005, 0.004, 0.013],            # cell (0, 0, 0)
+                      [0.995, 0.995, 0.988], [0.996, 0.995, 0.987],            # cell (127, 127, 63)
+                      [0.001, 0.001, 0.001], [0.999, 0.999, 0.999]])           # cell 0 and the last cell, through the corner
+    pos = np.concatenate([pairs, np.random.RandomState(21).uniform(0.02, 0.98, (294, 3))])
+    roots = fn.groups_loop(pos, (1., 1., 1.), ell)[0]
+    for v in (pos, roots):
+        v.setflags(write=False)
+    return pos, (1., 1., 1.), ell, roots
+
+
 def all_cases():
     return [case_a(), case_b(), case_c(2.5), case_c(3.9), case_d(1.0), case_d(1.0 + 2. ** -40), case_e("index"),
             case_e("reversed"), case_e("shuffled"), case_f_coincident(), case_f_outside()]

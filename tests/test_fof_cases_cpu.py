@@ -102,3 +102,20 @@ def test_default_particle_mass_convention():
     # 3 H0^2 / (8 pi G) with H0 = 100 h km/s/Mpc, G = 4.30091e-9 Mpc (km/s)^2 / Msun
     rho = 3. * (100. * h) ** 2 / (8. * np.pi * 4.30091e-9)
     assert abs(rho / (halos.RHO_CRIT * h * h) - 1.) < 1e-4 and 0.2 < om < 0.4
+
+
+def test_case_g_three_pairs_in_the_corner_cells():
+    """The case of the raw link call on 128 x 128 x 64 cells: a pair in cell 0, a pair in the last cell, a pair through the
+    periodic corner between those two cells, everything else single; cells no smaller than the linking length."""
+    pos, L, ell, roots = fc.case_g_many_cells()
+    n, cells = pos.shape[0], np.array(fc.G_CELLS)
+    assert n == 300 and np.all(np.array(L) / cells >= ell) and ell > 0.999 / 128.
+    assert cells.prod() + 1 == 256 * 4096 + 1                            # the scan's outputs: one past 256 chunks
+    np.testing.assert_array_equal(roots, fn.groups_tree(pos, L, ell))
+    np.testing.assert_array_equal(roots[:6], [0, 0, 2, 2, 4, 4])
+    np.testing.assert_array_equal(roots[6:], np.arange(6, n))
+    assert fn.groups_loop(pos, L, ell)[1] >= 1e-3                         # no pair near the linking length
+    idx = np.minimum((fn.wrap(pos, np.array(L)) * cells).astype(int), cells - 1)
+    cell = (idx[:, 0] * cells[1] + idx[:, 1]) * cells[2] + idx[:, 2]
+    np.testing.assert_array_equal(cell[:6], [0, 0, cells.prod() - 1, cells.prod() - 1, 0, cells.prod() - 1])
+    assert np.unique(cell[6:]).size > 250 and cell[6:].min() > 0 and cell[6:].max() < cells.prod() - 1

@@ -67,6 +67,41 @@ def test_constructed_cases_equal_the_reference(index, prec):
     _check(_find(case, prec), case, cat)
 
 
+@pytest.mark.parametrize("prec", PRECS)
+def test_many_cells_scan_carries_across_rounds(prec):
+    """fb_fof_link itself on 128 x 128 x 64 cells of the unit box: the scan of the cell histogram writes 2^20 + 1 offsets, 257
+    chunks of 4096, so the one workgroup that scans the chunk sums takes a second round of 256 and carries the running sum
+    into it -- the offsets of the last cell, and start[ncells] = n, come from that round.  Roots and group sizes equal the
+    definition's exactly (what the case holds is asserted by tests/test_fof_cases_cpu.py)."""
+    import ctypes
+    pos, L, ell, roots = fc.case_g_many_cells()
+    n, ncells = pos.shape[0], fc.G_CELLS[0] * fc.G_CELLS[1] * fc.G_CELLS[2]
+    box = _box(L, prec)
+    eng = box.engine
+    wbytes = int(eng.lib.fb_fof_work_bytes(n, ncells))
+    assert 8 * ncells < wbytes < 8 * ncells + (1 << 20)              # about 8 MiB: the cell table and its cursors
+    pbuf, work, root = eng.upload_raw(pos), eng._alloc_bytes(wbytes), eng._alloc_bytes(4 * n)
+    bad = ctypes.c_int32(0)
+    _lib.call("fb_fof_link", eng._plan, pbuf.ptr, n, ell, (ctypes.c_int32 * 3)(*fc.G_CELLS), work.ptr, wbytes, root.ptr,
+              ctypes.byref(bad), None, eng.stream)
+    assert not bad.value
+    count, small, kept = eng._alloc_bytes(4 * n), eng._alloc_bytes(256), eng._alloc_bytes(8 * n)
+    out = (ctypes.c_int64 * 2)()
+    _lib.call("fb_fof_sizes", eng._plan, root.ptr, n, 1, small.ptr, count.ptr, kept.ptr, out, eng.stream)
+    got = np.empty(n, dtype=np.uint32)
+    pairs = np.empty((n, 2), dtype=np.uint32)
+    _lib.call("fb_memcpy_d2h", got.ctypes.data_as(ctypes.c_void_p), root.ptr, got.nbytes, eng.stream)
+    _lib.call("fb_memcpy_d2h", pairs.ctypes.data_as(ctypes.c_void_p), kept.ptr, pairs.nbytes, eng.stream)
+    eng.sync()
+    np.testing.assert_array_equal(got, roots)
+    uniq, cnt = np.unique(roots, return_counts=True)
+    assert (int(out[0]), int(out[1])) == (uniq.size, uniq.size)
+    pairs = pairs[:uniq.size]
+    pairs = pairs[np.argsort(pairs[:, 0])]
+    np.testing.assert_array_equal(pairs[:, 0], uniq)
+    np.testing.assert_array_equal(pairs[:, 1], cnt)
+
+
 def test_default_particle_mass():
     case, _ = fc.reference(0)
     h = _find(case, "f64")

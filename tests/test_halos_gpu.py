@@ -144,6 +144,25 @@ def test_catalogue_with_large_counts(prec):
     np.testing.assert_array_equal(np.asarray(cat), hn.catalogue(c, L))
 
 
+@pytest.mark.parametrize("prec", PRECS)
+def test_catalogue_table_scan_carries_across_rounds(prec):
+    """A count of 16384 at 64^3 (64 tiles of 4096 voxels): the (count, tile) table has 16385 x 64 = 1048640 entries, 257 chunks
+    of 4096, so the one workgroup that scans the chunk sums takes a second round of 256 and carries the running sum into it.
+    The entries of count 16384 are the ones of chunk 256: their halos start after everything else, the second voxel's after
+    the first's."""
+    N, L = 64, (640., 650., 660.)
+    box = _box(N, L, prec)
+    hd = HaloDistribution(box, (1e12, 1e15), 10)
+    c = np.zeros((N, N, N), dtype=np.int64)
+    c[0, 0, 5], c[2, 3, 4], c[63, 63, 63] = 1, 3, 2                     # tiles 0, 2 and 63
+    c[20, 1, 1], c[40, 40, 40] = 4097, 9000                             # past the LDS histogram, chunks 64 and 140
+    c[3, 10, 7], c[60, 2, 9] = 16384, 16384                             # chunk 256, tiles 3 and 60
+    assert (c.max() + 1) * (N ** 3 // 4096) == 1048640 and -(-1048641 // 4096) == 257
+    cat = hd.realise_halo_catalogue(c)
+    assert len(cat) == c.sum()
+    np.testing.assert_array_equal(np.asarray(cat), hn.catalogue(c, L))
+
+
 # ---- 3. painting -------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("prec", PRECS)
 @pytest.mark.parametrize("window", ["ngp", "cic", "tsc"])
