@@ -73,7 +73,14 @@ SIGNATURES = {
     "fb_correlation_function": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, P_double, c_int, c_int,
                                         P_double, c_void_p]),
     "fb_bin_power_kmu": (c_int, [c_void_p, c_void_p, c_void_p, P_double, c_int, c_int, c_int, P_double, c_void_p]),
-    "fb_power_spectrum_kmu": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, P_double, c_int, c_int, c_int,
+    "fb_bin_power_cyl": (c_int, [c_void_p, c_void_p, c_void_p, P_double, c_int, P_double, c_int, P_double, c_void_p]),
+    "fb_power_spectrum_cyl": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, P_double, c_int, P_double, c_int,
+                                      P_double, c_void_p]),
+    "fb_transverse_gram_work_bytes": (c_i64, [c_void_p, c_int, c_int]),
+    "fb_transverse_gram": (c_int, [c_void_p, c_void_p, c_void_p, P_double, c_int, c_void_p, c_void_p, P_double, c_void_p]),
+    "fb_angular_power": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, P_double, c_int, c_void_p, c_void_p,
+                                 P_double, c_void_p]),
+    "fb_power_spectrum_kmu": (c_int,[c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, P_double, c_int, c_int, c_int,
                                       P_double, c_void_p]),
     "fb_bispectrum": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, P_double, c_int, c_int, P_double,
                               c_void_p]),

@@ -1008,6 +1008,81 @@ class CosmoBox(object):
             return k, mu, power, modes
         return k[:, 0].copy(), (power[:, 0].copy() if ps is None else power), modes[:, 0].copy()
 
+    # ------------------------------------------------------------ cylindrical power, multi-frequency angular power
+    def cylindrical_power_spectrum(self, delta_x=None, second=None, kperp_bins=None, kpar_bins=None, dk_perp=None,
+                                   kperp_min=0., kperp_max=None):
+        """Additive: the cylindrical power spectrum P(k_perp, k_par) of a real field (or the cross spectrum with ``second``),
+        line of sight z -- the plane in which the foreground wedge, a beam's cut-off and the damage of a cleaning step are read
+        off.  With the conventions of ``power_spectrum``:
+
+            D_a = rfftn(d_a) (unnormalised),  P(k) = (Lx Ly Lz / N^6) Re(conj(D_1) D_2)   (fp64);
+            k_a = m_a (2 pi / L_a) (m_a the signed FFT index), k_perp = sqrt(k_x k_x + k_y k_y), k_par = |k_z|;
+            every mode of the full grid but k = 0; bins [e_b, e_b+1) on both axes (np.digitize - 1), modes outside dropped;
+            per cell: modes, kperp = mean k_perp, kpar = mean k_par, power = mean P.
+
+        Returns ``(kperp, kpar, power, modes)``, each (nperp, npar), float64, writeable.  Edges: ``kperp_bins``, or
+        np.arange(kperp_min, kperp_max + dk_perp/2, dk_perp) with dk_perp = 2 pi / min(Lx, Ly), kperp_max = pi N / max(Lx, Ly)
+        by default; ``kpar_bins``, or one bin around every |m_z|: (np.arange(N/2 + 2) - 0.5) 2 pi / Lz (N/2 + 1 bins).  The last
+        edge of either may be inf.  1 <= nperp <= 1024, 1 <= npar <= 1025; every grid.  Empty cells are NaN in kperp, kpar and
+        power.  Sums are fp64 in a fixed order: two calls agree bit for bit.  ``delta_x`` (default ``self.delta_x``) and
+        ``second`` take whatever ``power_spectrum`` takes.  The box's state (delta_x, stored spectrum, realisation counter,
+        P(k) bins) is left as it was.  Bad arguments raise ValueError before any device work."""
+        perp, par = hostgeom.cyl_edges((self.Lx, self.Ly, self.Lz), self.N, kperp_bins=kperp_bins, kpar_bins=kpar_bins,
+                                       dk_perp=dk_perp, kperp_min=kperp_min, kperp_max=kperp_max)
+        d1, d2 = self._two_fields(delta_x, second)
+        raw = self.engine.power_cyl(d1, d2, perp, par)
+        return hostgeom.finish_cyl(raw, perp.size - 1, par.size - 1)
+
+    def angular_power_spectrum(self, delta_x=None, second=None, kperp_bins=None, dk_perp=None, kperp_min=None,
+                               kperp_max=None, collapse=False, angular=False, redshift=None):
+        """Additive: the multi-frequency angular power spectrum of a cube whose last axis is frequency (the flat-sky
+        C_l(nu, nu') of Datta et al. 2007 and Mondal et al. 2018), or the cross spectrum with ``second``: the covariance of
+        the channels per angular scale, which shows whether spectrally smooth components were removed.
+
+            a_a(m_perp, nu) = np.fft.fftn(d_a, axes=(0, 1)) (unnormalised), every m_perp of the N x N plane but m_perp = 0;
+            C_b(nu, nu') = (Lx Ly / N^4) (1 / modes_b) sum_{m_perp in b} Re(a_1(m_perp, nu) conj(a_2(m_perp, nu')));
+            k_perp and its bins as in ``cylindrical_power_spectrum``.
+
+        Returns ``(kperp, cl, modes)``: kperp (nb,) the mean k_perp of each bin, cl (nb, N, N) float64 in Mpc^2 x field^2,
+        modes (nb,) int64.  The first channel index belongs to ``delta_x``, the second to ``second``; the auto result is
+        symmetric bit for bit.  Empty bins are NaN in kperp and cl.  Edges: ``kperp_bins``, or np.arange(kperp_min,
+        kperp_max + dk_perp/2, dk_perp) with dk_perp = 2 pi / min(Lx, Ly), kperp_min = dk_perp / 2 for the default dk_perp
+        (half the fundamental) and kperp_max = pi N / max(Lx, Ly); 1 <= nb <= 256, N <= 1024.  ``collapse=True``: cl is (nb, N),
+        the mean of C_b(nu, nu + D) over the N - D pairs.  ``angular=True``: returns l = k_perp r and C / r^2 with
+        r = comoving_angular_distance(cosmo, 1 / (1 + redshift)) (``redshift`` defaults to the box's), the distance
+        ``pixel_array`` uses.  The work memory (a complex cube per field, the partial sums and the result) must fit in device
+        memory: MemoryError before any kernel runs otherwise.  Operands are held in the box's precision, products and sums
+        are fp64 on the matrix cores in a fixed order (two calls agree bit for bit).  The box's state is left as it was.  Bad
+        arguments raise ValueError before any device work."""
+        N = self.N
+        edges = hostgeom.maps_edges((self.Lx, self.Ly, self.Lz), N, kperp_bins=kperp_bins, dk_perp=dk_perp,
+                                    kperp_min=kperp_min, kperp_max=kperp_max)
+        nb = edges.size - 1
+        if angular:
+            z = self.redshift if redshift is None else redshift
+            if not np.isfinite(z) or z <= -1.:
+                raise ValueError("redshift must be finite and > -1, got %r" % (redshift,))
+        for name, f in (("delta_x", delta_x), ("second", second)):     # (the checks of _two_fields, ahead of the memory check)
+            if isinstance(f, DeviceArray):
+                if f.engine is not self.engine or f.kind != REAL:
+                    raise ValueError("%s: a real field of this box" % name)
+            elif f is not None and np.shape(f) != (N, N, N):
+                raise ValueError("%s: expected an array of shape %s, got %s" % (name, (N, N, N), np.shape(f)))
+        eng = self.engine
+        need, have = eng.angular_power_bytes(nb, second is not None), eng.free_bytes()
+        if need > have:
+            raise MemoryError("angular_power_spectrum: %d bins of %d^2 channels and their work cubes take %.1f GiB, %.1f GiB "
+                              "are free" % (nb, N, need / 2. ** 30, have / 2. ** 30))
+        d1, d2 = self._two_fields(delta_x, second)
+        raw, cl = eng.angular_power(d1, d2, edges)
+        kperp, modes = hostgeom.finish_maps(raw, nb)
+        if collapse:
+            cl = hostgeom.collapse_maps(cl)
+        if angular:
+            r = _ccl.comoving_angular_distance(self.cosmo, 1. / (1. + z))
+            return kperp * r, cl / r ** 2, modes
+        return kperp, cl, modes
+
     # ------------------------------------------------------------ bispectrum in triangle bins
     def bispectrum(self, delta_x=None, kbins=None, dk=None, kmin=0., kmax=None, reduced=False):
         """Additive: the bispectrum of a real field in bins of three |k| shells, by the FFT estimator (Scoccimarro 2000;

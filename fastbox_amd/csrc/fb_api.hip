@@ -130,8 +130,10 @@ int fb_plan_destroy(fb_plan* p) {
     (void)hipSetDevice(p->device);
     void* ptrs[] = {p->tw, p->axis2, p->ksc, p->kpar, p->zgrid, p->amp_shell, p->amp_sym, p->kperp_tab, p->pca_work, p->bins, p->thr, p->counts,
                     p->partials, p->scratch, p->bin_partials, p->exp_partials, p->plane_buf, p->sep_edges, p->sep_partials,
-                    p->halo_small, p->halo_work, p->halo_acc, p->pk_tab, p->pk_partials, p->void_small, p->void_work};
+                    p->halo_small, p->halo_work, p->halo_acc, p->pk_tab, p->pk_partials, p->void_small, p->void_work,
+                    p->cyl_idx, p->cyl_tab, p->cyl_partials};
     for (void* q : ptrs) if (q) (void)hipFree(q);
+    fb_cyl_release(p);
     if (p->aux_stream) { (void)hipStreamSynchronize(p->aux_stream); (void)hipStreamDestroy(p->aux_stream); }
     if (p->ev_fork) (void)hipEventDestroy(p->ev_fork);
     if (p->ev_join) (void)hipEventDestroy(p->ev_join);

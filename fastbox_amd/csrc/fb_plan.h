@@ -14,6 +14,7 @@
 #define FB_ERR_RCCL -6
 
 struct fb_comm;                  // fb_comm.inc: RCCL communicator + its stream and events (fb_comm_create)
+struct fb_cyl_rows;              // fb_cyl.hip: one k_perp edge set's sorted transverse rows
 
 struct fb_plan {
     fb_comm* comm = nullptr;     // one box over several GPUs: this rank's communicator, or null
@@ -89,6 +90,16 @@ struct fb_plan {
     double* pk_partials = nullptr;    // [values][workgroups] of k_pk_bin (grown on demand)
     size_t pk_partials_cap = 0;
     std::vector<std::vector<double>> pk_geom;
+
+    // cylindrical power and multi-frequency angular power (fb_cyl.hip): the transverse rows sorted by k_perp bin per edge set
+    // already seen (most recent last; freed by fb_cyl_release), the chunk / fold tables of the call in flight, the partials
+    std::vector<fb_cyl_rows*> cyl_rows;
+    int* cyl_idx = nullptr;           // [3 chunks][nb + 1 chunk offsets][2 npar m_z ranges] (grown on demand)
+    size_t cyl_idx_cap = 0;
+    double* cyl_tab = nullptr;        // [nb] Lx Ly / (N^4 modes_b) of fb_transverse_gram (grown on demand)
+    size_t cyl_tab_cap = 0;
+    double* cyl_partials = nullptr;   // [chunks][N/2 + 1] of k_cyl_rows (grown on demand)
+    size_t cyl_partials_cap = 0;
 
     // halo tracers (fb_halo.hip): reduction partials, the catalogue's (count, block) tables, the painting accumulators
     void* halo_small = nullptr;       // [FB_HALO_SMALL] bytes
@@ -253,4 +264,5 @@ static inline int ensure_bytes(void** buf, size_t* cap, size_t need) {
 FB_DECL(f32)
 FB_DECL(f64)
 int fbi_bin_count(fb_plan* p, hipStream_t s);
+void fb_cyl_release(fb_plan* p);     // fb_cyl.hip: frees the plan's sorted-row lists (fb_plan_destroy)
 int fbi_slab_permute(fb_plan* p, const void* in, void* out, int nxl, int nparts, int pack, hipStream_t s);

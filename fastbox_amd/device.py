@@ -717,8 +717,48 @@ class Engine(object):
                   out.ctypes.data_as(_lib.P_double), self.stream)
         return out
 
+    # -- cylindrical power and multi-frequency angular power ---------------------------------------
+    def power_cyl(self, real1, real2, perp_edges, par_edges):
+        """fb_power_spectrum_cyl: the record [modes, sum k_perp, sum k_par, sum P per (k_perp, k_par) cell] (host, fp64) of
+        the auto- (real2 None) or cross-spectrum of two real device fields.  Work buffers come from the pool; waits for the
+        stream."""
+        pe = np.ascontiguousarray(perp_edges, dtype=np.float64)
+        qe = np.ascontiguousarray(par_edges, dtype=np.float64)
+        nperp, npar = pe.size - 1, qe.size - 1
+        out = np.zeros(4 * nperp * npar)
+        wh1 = self.empty(HALF)
+        wh2 = self.empty(HALF) if real2 is not None else None
+        _lib.call("fb_power_spectrum_cyl", self._plan, real1.ptr, real2.ptr if real2 is not None else None, wh1.ptr,
+                  wh2.ptr if wh2 is not None else None, pe.ctypes.data_as(_lib.P_double), nperp,
+                  qe.ctypes.data_as(_lib.P_double), npar, out.ctypes.data_as(_lib.P_double), self.stream)
+        return out
+
+    def angular_power_bytes(self, nb, cross):
+        """Device bytes fb_angular_power needs beside the fields: one complex cube per field, the per-(bin, slice) partials
+        and the nb N^2 doubles of the result."""
+        work = _lib.load().fb_transverse_gram_work_bytes(self._plan, int(nb), 1 if cross else 0)
+        return (2 if cross else 1) * self.nbytes[FULL] + work + nb * self.N * self.N * 8
+
+    def angular_power(self, real1, real2, perp_edges):
+        """fb_angular_power: (the record [modes, sum k_perp per bin], cl (nb, N, N)) (host, fp64) of the auto- (real2 None)
+        or cross-spectrum of two real device cubes.  Work buffers come from the pool; waits for the stream."""
+        pe = np.ascontiguousarray(perp_edges, dtype=np.float64)
+        nb, N = pe.size - 1, self.N
+        cross = real2 is not None
+        out = np.zeros(2 * nb)
+        cl = np.empty((nb, N, N))
+        wf1 = self.empty(FULL)
+        wf2 = self.empty(FULL) if cross else None
+        work = self._alloc_bytes(_lib.load().fb_transverse_gram_work_bytes(self._plan, nb, 1 if cross else 0))
+        cl_dev = self._alloc_bytes(cl.nbytes)
+        _lib.call("fb_angular_power", self._plan, real1.ptr, real2.ptr if cross else None, wf1.ptr,
+                  wf2.ptr if cross else None, pe.ctypes.data_as(_lib.P_double), nb, cl_dev.ptr, work.ptr,
+                  out.ctypes.data_as(_lib.P_double), self.stream)
+        _lib.call("fb_memcpy_d2h", cl.ctypes.data_as(ctypes.c_void_p), cl_dev.ptr, cl.nbytes, self.stream)
+        return out, cl
+
     # -- bispectrum in triangle bins -----------------------------------------------------------
-    BK_SPLIT = 4        # shells written per read of the spectrum (FB_BK_SPLIT of the library)
+    BK_SPLIT = 4       # shells written per read of the spectrum (FB_BK_SPLIT of the library)
 
     def bispectrum_bytes(self, nb):
         """Device bytes fb_bispectrum needs beside the field: nb real cubes, the spectrum and the shells of one batch."""

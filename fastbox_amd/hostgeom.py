@@ -342,6 +342,90 @@ def finish_power(raw, nk, nmu, poles=None):
     return k, mu, power, modes
 
 
+# ---- cylindrical power and multi-frequency angular power (CosmoBox.cylindrical_power_spectrum, .angular_power_spectrum) ------
+CYL_MAX_PERP = 1024          # FB_CYL_MAX_PERP of the library: dk_perp = 2 pi / L up to Nyquist at N = 2048
+CYL_MAX_PAR = 1025           # FB_CYL_MAX_PAR: one bin per |m_z| at N = 2048
+MAPS_MAX_BINS = 256          # FB_MAPS_MAX_BINS
+MAPS_MAX_N = 1024            # FB_MAPS_MAX_N
+
+
+def _perp_edges(L, N, kperp_bins, dk_perp, kperp_min, kperp_max, most):
+    """k_perp edges: ``kperp_bins`` as given, or np.arange(kperp_min, kperp_max + dk_perp/2, dk_perp) with
+    dk_perp = 2 pi / min(Lx, Ly) and kperp_max = pi N / max(Lx, Ly) by default.  The checks and messages of power_edges."""
+    if kperp_bins is not None:
+        edges = np.array(kperp_bins, dtype=np.float64)
+    else:
+        dk = 2. * np.pi / float(min(L[0], L[1])) if dk_perp is None else float(dk_perp)
+        kmax = np.pi * N / float(max(L[0], L[1])) if kperp_max is None else float(kperp_max)
+        if not dk > 0:
+            raise ValueError("dk must be positive")
+        edges = np.arange(float(kperp_min), kmax + 0.5 * dk, dk, dtype=np.float64)
+    if edges.ndim != 1 or edges.size < 2 or edges.size > most + 1:
+        raise ValueError("k bins: between 2 and %d edges (1 to %d bins), got %r" % (most + 1, most, edges.shape))
+    if not np.all(np.isfinite(edges[:-1])) or not edges[0] >= 0. or not np.all(np.diff(edges) > 0):
+        raise ValueError("k bin edges must be strictly ascending and start at >= 0")
+    return edges
+
+
+def cyl_edges(L, N, kperp_bins=None, kpar_bins=None, dk_perp=None, kperp_min=0., kperp_max=None):
+    """(k_perp edges, k_par edges) of the cylindrical power spectrum.  k_perp: ``kperp_bins``, or
+    np.arange(kperp_min, kperp_max + dk_perp/2, dk_perp) with dk_perp = 2 pi / min(Lx, Ly), kperp_max = pi N / max(Lx, Ly);
+    strictly ascending, first edge >= 0, all finite but the last, 1 to 1024 bins.  k_par: ``kpar_bins``, or one bin around
+    every |m_z|, (np.arange(N/2 + 2) - 0.5) 2 pi / Lz (N/2 + 1 bins); strictly ascending, all finite but the last (the first
+    may be negative: k_par = |k_z| >= 0 anyway), 1 to 1025 bins.  ValueError otherwise."""
+    perp = _perp_edges(L, N, kperp_bins, dk_perp, kperp_min, kperp_max, CYL_MAX_PERP)
+    if kpar_bins is not None:
+        par = np.array(kpar_bins, dtype=np.float64)
+    else:
+        par = (np.arange(N // 2 + 2) - 0.5) * (2. * np.pi / float(L[2]))
+    if par.ndim != 1 or par.size < 2 or par.size > CYL_MAX_PAR + 1:
+        raise ValueError("k bins: between 2 and %d edges (1 to %d bins), got %r" % (CYL_MAX_PAR + 1, CYL_MAX_PAR, par.shape))
+    if not np.all(np.isfinite(par[:-1])) or not np.all(np.diff(par) > 0):
+        raise ValueError("k_par bin edges must be strictly ascending")
+    return perp, par
+
+
+def maps_edges(L, N, kperp_bins=None, dk_perp=None, kperp_min=None, kperp_max=None):
+    """k_perp edges of the multi-frequency angular power spectrum: as cyl_edges, but starting at half the fundamental
+    (kperp_min = pi / min(Lx, Ly)) by default, 1 to 256 bins, and N <= 1024.  ValueError otherwise."""
+    if N > MAPS_MAX_N:
+        raise ValueError("angular_power_spectrum: grids up to %d^3" % MAPS_MAX_N)
+    if kperp_min is None:
+        kperp_min = np.pi / float(min(L[0], L[1]))
+    return _perp_edges(L, N, kperp_bins, dk_perp, kperp_min, kperp_max, MAPS_MAX_BINS)
+
+
+def finish_cyl(raw, nperp, npar):
+    """From fb_bin_power_cyl's record [modes, sum k_perp, sum k_par, sum P (nperp * npar each)]: (kperp, kpar, power, modes),
+    each (nperp, npar), the first three the means per cell (NaN where modes is 0)."""
+    raw = np.asarray(raw, dtype=np.float64)
+    nc = nperp * npar
+    modes, sperp, spar, sp = (raw[q * nc:(q + 1) * nc].reshape(nperp, npar).copy() for q in range(4))
+    with np.errstate(all="ignore"):
+        empty = modes == 0
+        return (np.where(empty, np.nan, sperp / modes), np.where(empty, np.nan, spar / modes),
+                np.where(empty, np.nan, sp / modes), modes)
+
+
+def finish_maps(raw, nb):
+    """From fb_transverse_gram's record [modes, sum k_perp (nb each)]: (kperp (nb,) float64, the mean per bin, NaN where the
+    bin is empty; modes (nb,) int64)."""
+    raw = np.asarray(raw, dtype=np.float64)
+    modes, sk = raw[:nb], raw[nb:2 * nb]
+    with np.errstate(all="ignore"):
+        kperp = np.where(modes == 0, np.nan, sk / modes)
+    return kperp, np.rint(modes).astype(np.int64)
+
+
+def collapse_maps(cl):
+    """(nb, N) from (nb, N, N): out[b, D] = the mean of cl[b, nu, nu + D] over the N - D pairs of channels D apart."""
+    cl = np.asarray(cl, dtype=np.float64)
+    if cl.ndim != 3 or cl.shape[1] != cl.shape[2]:
+        raise ValueError("collapse_maps: expected an array of shape (nb, N, N), got %r" % (cl.shape,))
+    N = cl.shape[1]
+    return np.stack([np.trace(cl, offset=D, axis1=1, axis2=2) / float(N - D) for D in range(N)], axis=1)
+
+
 # ---- bispectrum in triangle bins (CosmoBox.bispectrum) ---------------------------------------------------------------------
 BK_MAX_SHELLS = 32           # FB_BK_MAX_SHELLS of the library: two 16-row tiles of the contraction
 BK_DEFAULT_SHELLS = 16

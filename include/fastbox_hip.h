@@ -236,6 +236,49 @@ int fb_bin_power_kmu(fb_plan* plan, const void* half1, const void* half2, const 
 int fb_power_spectrum_kmu(fb_plan* plan, const void* real1, const void* real2, void* work_half1, void* work_half2,
                           const double* kedges, int nk, int nmu, int lmax, double* out_host, void* stream);
 
+/* ---- cylindrical power P(k_perp, k_par) and multi-frequency angular power C(k_perp; nu, nu') ------------------------- */
+/* Two estimators that bin the transverse modes (m_x, m_y) in k_perp and keep the line of sight (z, the frequency axis)
+ * resolved.  The reference and nbodykit have neither: these definitions are the contract.  Conventions are those of
+ * fb_bin_power_kmu: k_a = m_a (2 pi / L_a), m_a the signed index (Nyquist negative); k_perp = sqrt(k_x k_x + k_y k_y) in fp64,
+ * no contraction; k_perp bin b = np.digitize(k_perp, perp_edges) - 1, modes outside [perp_edges[0], perp_edges[n]) dropped;
+ * products and sums in fp64 in a fixed order without atomics (two calls agree bit for bit).
+ *
+ * Cylindrical power, for real fields d_1, d_2 (auto: d_2 = d_1):
+ *   D_a = rfftn(d_a) (unnormalised); P(k) = (Lx Ly Lz / N^6) Re(conj(D_1(k)) D_2(k)); k_par = |k_z|; k_par bin
+ *   c = np.digitize(k_par, par_edges) - 1.  Modes of the full grid: a half-spectrum cell with 0 < m_z < N/2 counts twice, the
+ *   planes m_z = 0 and N/2 once; k = 0 is excluded.  Cell (b, c) has index b npar + c.
+ * Limits (FB_ERR_INVALID otherwise): perp_edges[nperp + 1] strictly ascending, perp_edges[0] >= 0, all finite but the last
+ *   (which may be inf); par_edges[npar + 1] strictly ascending, all finite but the last (the first may be negative: the
+ *   default edges put one bin around every |m_z|); 1 <= nperp <= 1024; 1 <= npar <= 1025.
+ * fb_bin_power_cyl: bins Re(conj(half1) half2) (half2 = NULL: |half1|^2) straight from the stored half spectra.
+ *   out_host[4 nperp npar] (nc = nperp npar): modes[nc], sum_kperp[nc], sum_kpar[nc], sum_p[nc]; the columns of a cell are
+ *   kperp = sum_kperp / modes, kpar = sum_kpar / modes, power = sum_p / modes.  The transverse rows sorted by k_perp bin are
+ *   built once per perp_edges and kept in the plan (the eight most recent edge sets).  Synchronises the stream.
+ * fb_power_spectrum_cyl: fb_fft_r2c of real1 (and real2; NULL: auto spectrum) into work_half1 (work_half2), then
+ *   fb_bin_power_cyl.  Every grid a plan accepts.  Synchronises.
+ *
+ * Multi-frequency angular power (the flat-sky C_l(nu, nu') of Datta et al. 2007, Mondal et al. 2018), for real cubes d_1, d_2:
+ *   a_a(m_perp, nu) = np.fft.fftn(d_a, axes=(0, 1)) (unnormalised), every m_perp of the full N x N plane but m_perp = 0;
+ *   C_b(nu, nu') = (Lx Ly / N^4) (1 / modes_b) sum_{m_perp in b} Re(a_1(m_perp, nu) conj(a_2(m_perp, nu'))).
+ *   The first channel index belongs to cube 1, the second to cube 2; the auto result is symmetric bit for bit.  An empty bin
+ *   is NaN.  The operands are held in the plan's precision and converted to fp64 on load; the sums run on the fp64 matrix cores.
+ * Limits (FB_ERR_INVALID otherwise): perp_edges as above; 1 <= nb <= 256; N <= 1024.
+ * fb_transverse_gram: full1, full2 (NULL: auto) are complex [N][N][N] cubes already transformed by fb_fft_transverse(-1).
+ *   cl_dev[nb][N][N] (device, fp64) receives C_b; work_dev: fb_transverse_gram_work_bytes(plan, nb, cross) bytes of device
+ *   memory for the per-(bin, slice) partials; out_host[2 nb]: modes[nb], sum_kperp[nb].  Synchronises.
+ * fb_angular_power: fb_real_to_complex and fb_fft_transverse(-1) of real1 into work_full1 (and of real2, if given, into
+ *   work_full2), then fb_transverse_gram.  Synchronises. */
+int fb_bin_power_cyl(fb_plan* plan, const void* half1, const void* half2, const double* perp_edges, int nperp,
+                     const double* par_edges, int npar, double* out_host, void* stream);
+int fb_power_spectrum_cyl(fb_plan* plan, const void* real1, const void* real2, void* work_half1, void* work_half2,
+                          const double* perp_edges, int nperp, const double* par_edges, int npar, double* out_host,
+                          void* stream);
+long long fb_transverse_gram_work_bytes(const fb_plan* plan, int nb, int cross);
+int fb_transverse_gram(fb_plan* plan, const void* full1, const void* full2, const double* perp_edges, int nb, double* cl_dev,
+                       void* work_dev, double* out_host, void* stream);
+int fb_angular_power(fb_plan* plan, const void* real1, const void* real2, void* work_full1, void* work_full2,
+                     const double* perp_edges, int nb, double* cl_dev, void* work_dev, double* out_host, void* stream);
+
 /* ---- bispectrum in triangle bins ----------------------------------------------------------------------------------- */
 /* The FFT estimator of the bispectrum of a real field d (Scoccimarro 2000; Sefusatti et al. 2016) in bins of three |k| shells.
  * The reference and nbodykit have none: this definition is the contract.  It follows the conventions of fb_bin_power_kmu:
