@@ -13,6 +13,8 @@ from .device import DeviceArray                   # noqa: F401
 from .sky import ForegroundModel, NoiseModel      # noqa: F401
 from . import filters                             # noqa: F401
 from . import inpaint                             # noqa: F401
+from . import losfit                              # noqa: F401
+from .losfit import GPRKernel, LSQfitting         # noqa: F401
 from . import analysis                            # noqa: F401
 from . import montecarlo                          # noqa: F401
 from .beams import BeamModel                      # noqa: F401

@@ -142,6 +142,11 @@ SIGNATURES = {
     "fb_gcr_finish": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_u64, c_u64, c_void_p,
                               c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "fb_replace_nan_channel_mean": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fb_los_polyfit": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                               c_void_p, c_void_p, P_i32, c_void_p]),
+    "fb_los_powerlaw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_double, c_void_p, c_int,
+                                c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, P_i32, c_void_p]),
+    "fb_los_subtract": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fb_sky_realise_map": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_double, c_void_p, c_void_p, c_void_p]),
     "fb_sky_normal_map": (c_int, [c_void_p, c_void_p, c_u64, c_double, c_double, c_void_p, c_void_p]),
     "fb_sky_gaussian_filter": (c_int, [c_void_p, c_void_p, c_void_p, P_double, c_int, c_void_p]),

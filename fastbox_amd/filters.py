@@ -440,3 +440,7 @@ def bandpower_pca_filter(field, nbands, modes, box=None):
         cleaned = pca_filter(real, int(modes[i]))
         total = cleaned if total is None else eng.axpby(total, cleaned, 1.0, 1.0, 0.0)
     return total
+
+
+# polynomial_filter, LSQfitting and gpr_filter (filters.py:494-664): fits along the line of sight, in fastbox_amd/losfit.py
+from .losfit import (GPRKernel, GPRResult, LOSFit, LSQResult, LSQfitting, gpr_filter, polynomial_filter)    # noqa: E402,F401

@@ -679,6 +679,49 @@ int fb_gcr_finish(fb_plan* plan, const double* sqrtS_dev, const double* x, doubl
                   int inpaint, void* cube_out, void* stream);
 int fb_replace_nan_channel_mean(fb_plan* plan, const void* cube, void* cube_out, double* mean_dev, void* stream);
 
+/* ---- model fits along the line of sight (fastbox/filters.py:494-593 gpr_filter, :598-664 LSQfitting), fb_losfit.hip ----
+ * One wave per line of sight p (a row of the (N^2, N) view), all fit state fp64, every sum in a fixed order; N <= 1024.  w and
+ * sigma: NULL (1 everywhere), double[N] on the device (FB_GCR_PER_CHANNEL) or a cube in the plan's precision
+ * (FB_GCR_PER_VOXEL); w = 0 flags a voxel, whose datum is selected away and may be NaN.  status_dev[N^2]: FB_LOSFIT_* per row;
+ * a row with a status other than FB_LOSFIT_OK is NaN in every output.  n_failed_out (host): the number of such rows.  Both fit
+ * entries synchronise.  Definitions: DESIGN.md section 4.
+ *
+ * fb_los_polyfit: per row minimise sum_c w^2 (y_c - sum_k a_k basis_dev[k][c])^2, k = 0 .. order (order <= 7), y = T or, with
+ *   log_y, ln T.  basis_dev[order + 1][N] fp64: the basis at the channels (the caller's Legendre polynomials).  pinv_dev
+ *   (NULL, or [order + 1][N] fp64 with no or per-channel w): a_k = sum_c pinv_dev[k][c] y_c over the unflagged channels, the
+ *   shared pseudo-inverse with w folded in; without it every row accumulates its own normal matrix and solves it by Cholesky.
+ *   cube_out = T - model where w != 0 and exactly 0 elsewhere (model = exp(fit) with log_y).  model_out (may be NULL): the
+ *   model at every channel, flagged ones included, in the plan's precision.  coeffs_dev (may be NULL): double[order + 1][N^2].
+ *   chi2_dev (may be NULL): double[N^2], sum_c w^2 (y - fit)^2.  FB_LOSFIT_TOO_FEW: fewer unflagged channels than coefficients;
+ *   _NONFINITE: a non-finite unflagged datum; _NONPOSITIVE: an unflagged datum <= 0 with log_y; _SINGULAR: a pivot <= 0.
+ * fb_los_powerlaw: d = maps - tpsmean_dev[c] (NULL: 0), x = nu / nu_0 given as lnx_dev[N] = ln x.  Stage 1 minimises
+ *   sum_c (w (ampS x^betaS - d) / sigma)^2 over 0.5 d0 <= ampS <= 1.5 d0 and betaS between 0.9 b and 1.1 b, d0 the first
+ *   unflagged datum, b = beta_guess_dev[p] or, where that is NULL, ln(d3 / d0) / ln(x3 / x0) from the first and fourth
+ *   unflagged channels: for every betaS the best ampS in its interval is closed-form, and betaS takes Gauss-Newton steps
+ *   clipped to its interval and halved while the cost rises, until a step is below tol max(1, |betaS|) (at most max_iter
+ *   steps, at most max_iter halvings each).  Stage 2: amps = (S^T S)^-1 S^T d on the unflagged channels, S = [x^betaS,
+ *   x^freeind]; model = S amps; resid_out = d - model where w != 0 and exactly 0 elsewhere.  rows_dev: double[5][N^2] = betaS,
+ *   ampS, the two amps, the stage-1 cost (half the sum of squares).  n_iter_dev[N^2]: steps taken.  FB_LOSFIT_TOO_FEW: fewer
+ *   than four unflagged channels; _NONFINITE; _NONPOSITIVE: d0 <= 0 or d3 / d0 <= 0; _SINGULAR: a normal matrix is singular
+ *   (stage 2: det <= 1e-14 S11 S22); _MAXITER.
+ * fb_los_subtract: cube_out = X - shift_dev[c] - Y, X and cube_out cubes in the plan's precision, Y an fp64 cube: with
+ *   Y = M X from fb_los_matmul and shift = mean - M mean that is (I - M)(X - mean), the cleaned cube of the Gaussian-process
+ *   filter.  cube_out must not be X.                                                                                            */
+#define FB_LOSFIT_OK 0
+#define FB_LOSFIT_TOO_FEW 1
+#define FB_LOSFIT_NONFINITE 2
+#define FB_LOSFIT_NONPOSITIVE 3
+#define FB_LOSFIT_SINGULAR 4
+#define FB_LOSFIT_MAXITER 5
+int fb_los_polyfit(fb_plan* plan, const void* cube, const void* w, int w_kind, const double* basis_dev, const double* pinv_dev,
+                   int order, int log_y, void* cube_out, void* model_out, double* coeffs_dev, double* chi2_dev, int32_t* status_dev,
+                   int32_t* n_failed_out, void* stream);
+int fb_los_powerlaw(fb_plan* plan, const void* maps, const double* tpsmean_dev, const void* sigma, int sigma_kind, const void* w,
+                    int w_kind, const double* lnx_dev, double freeind, const double* beta_guess_dev, int max_iter, double tol,
+                    void* resid_out, void* model_out, double* rows_dev, int32_t* n_iter_dev, int32_t* status_dev,
+                    int32_t* n_failed_out, void* stream);
+int fb_los_subtract(fb_plan* plan, const void* X, const double* Y, const double* shift_dev, void* cube_out, void* stream);
+
 /* ---- the steps after the density-field path: foregrounds (fastbox/foregrounds.py:48-175) and radiometer
  * noise (fastbox/noise.py:25-75).  2-D maps are T[N][N] over (x, y); cubes T[N][N][N], frequency axis last. ---- */
 /* realise_foreground_amp (:99-107): map_out = Re ifft2((re + i im) amp2d) + monopole.  amp2d = sqrt(C_ell) per
