@@ -26,21 +26,19 @@ int fb_hip_check(hipError_t e, const char* what) {
 }
 
 namespace {
-template <typename T> int upload(T** dst, const T* src, size_t n) {
-    FB_HIP(hipMalloc(reinterpret_cast<void**>(dst), n * sizeof(T)));
-    FB_HIP(hipMemcpy(*dst, src, n * sizeof(T), hipMemcpyHostToDevice));
+template <typename B, typename T> int upload(B& dst, const T* src, size_t n) {
+    FB_TRY(dst.ensure(n * sizeof(T)));
+    FB_HIP(hipMemcpy(dst, src, n * sizeof(T), hipMemcpyHostToDevice));
     return FB_OK;
 }
-template <typename T> int make_twiddles(void** out, int N) {
+template <typename T> int make_twiddles(FbBuf<>& out, int N) {
     std::vector<T> h((size_t)2 * N);
     for (int j = 0; j < N; ++j) {
         const long double a = -2.0L * 3.14159265358979323846264338327950288L * (long double)j / (long double)N;
         h[2 * (size_t)j] = (T)cosl(a);
         h[2 * (size_t)j + 1] = (T)sinl(a);
     }
-    FB_HIP(hipMalloc(out, h.size() * sizeof(T)));
-    FB_HIP(hipMemcpy(*out, h.data(), h.size() * sizeof(T), hipMemcpyHostToDevice));
-    return FB_OK;
+    return upload(out, h.data(), h.size());
 }
 }  // namespace
 
@@ -99,24 +97,24 @@ int fb_plan_create(fb_plan** plan, int N, double Lx, double Ly, double Lz, int p
     p->NZV = N / 2 + 1;
     p->NZP = (p->NZV + 15) & ~15;
     p->NR = N + 1;
-    int r = precision == 4 ? make_twiddles<float>(&p->tw, N) : make_twiddles<double>(&p->tw, N);
-    if (!r) r = upload(&p->axis2, axis2, (size_t)3 * N);
-    if (!r) r = upload(&p->ksc, ksc, (size_t)3 * N);
-    if (!r) r = upload(&p->kpar, kpar, (size_t)N);
-    if (!r) r = upload(&p->zgrid, zgrid, (size_t)N);
+    int r = precision == 4 ? make_twiddles<float>(p->tw, N) : make_twiddles<double>(p->tw, N);
+    if (!r) r = upload(p->axis2, axis2, (size_t)3 * N);
+    if (!r) r = upload(p->ksc, ksc, (size_t)3 * N);
+    if (!r) r = upload(p->kpar, kpar, (size_t)N);
+    if (!r) r = upload(p->zgrid, zgrid, (size_t)N);
     if (!r) {          // k_perp per (k_x, k_y), the value kperp_exact() forms on the device (IEEE sqrt, same order)
         std::vector<double> kp((size_t)N * N);
         for (int i = 0; i < N; ++i)
             for (int j = 0; j < N; ++j) kp[(size_t)i * N + j] = FB_TWO_PI * std::sqrt(axis2[i] + axis2[N + j]);
-        r = upload(&p->kperp_tab, kp.data(), kp.size());
+        r = upload(p->kperp_tab, kp.data(), kp.size());
     }
     p->prow = 2048;      // 8 four-wave workgroups per CU
-    if (!r) r = fb_hip_check(hipMalloc((void**)&p->partials, (size_t)p->prow * 2 * FB_MAX_BINS * sizeof(double)), "hipMalloc");
-    if (!r) r = fb_hip_check(hipMalloc((void**)&p->scratch, FB_SCRATCH * sizeof(double)), "hipMalloc");
-    if (!r) r = fb_hip_check(hipMalloc((void**)&p->counts, FB_MAX_BINS * sizeof(unsigned long long)), "hipMalloc");
-    if (!r) r = fb_hip_check(hipMalloc((void**)&p->bins, FB_MAX_BINS * sizeof(double)), "hipMalloc");
-    if (!r) r = fb_hip_check(hipMalloc((void**)&p->thr, FB_MAX_BINS * sizeof(int)), "hipMalloc");
-    if (!r) r = fb_hip_check(hipMalloc((void**)&p->plane_buf, (size_t)N * N * 2 * precision), "hipMalloc");
+    if (!r) r = p->partials.ensure((size_t)p->prow * 2 * FB_MAX_BINS * sizeof(double));
+    if (!r) r = p->scratch.ensure(FB_SCRATCH * sizeof(double));
+    if (!r) r = p->counts.ensure(FB_MAX_BINS * sizeof(unsigned long long));
+    if (!r) r = p->bins.ensure(FB_MAX_BINS * sizeof(double));
+    if (!r) r = p->thr.ensure(FB_MAX_BINS * sizeof(int));
+    if (!r) r = p->plane_buf.ensure((size_t)N * N * 2 * precision);
     if (r) { fb_plan_destroy(p); return r; }
     p->nbins = 0;
     *plan = p;
@@ -128,17 +126,11 @@ int fb_plan_destroy(fb_plan* p) {
     if (!p) return FB_OK;
     (void)fb_comm_destroy(p);
     (void)hipSetDevice(p->device);
-    void* ptrs[] = {p->tw, p->axis2, p->ksc, p->kpar, p->zgrid, p->amp_shell, p->amp_sym, p->kperp_tab, p->pca_work, p->bins, p->thr, p->counts,
-                    p->partials, p->scratch, p->bin_partials, p->exp_partials, p->plane_buf, p->sep_edges, p->sep_partials,
-                    p->halo_small, p->halo_work, p->halo_acc, p->pk_tab, p->pk_partials, p->void_small, p->void_work,
-                    p->cyl_idx, p->cyl_tab, p->cyl_partials};
-    for (void* q : ptrs) if (q) (void)hipFree(q);
-    fb_cyl_release(p);
     if (p->aux_stream) { (void)hipStreamSynchronize(p->aux_stream); (void)hipStreamDestroy(p->aux_stream); }
     if (p->ev_fork) (void)hipEventDestroy(p->ev_fork);
     if (p->ev_join) (void)hipEventDestroy(p->ev_join);
     for (hipEvent_t e : p->prof_ev) (void)hipEventDestroy(e);
-    delete p;
+    delete p;            // frees the plan's device memory (FbBuf): its device is current
     return FB_OK;
 }
 
@@ -244,8 +236,7 @@ int bin_power_common(fb_plan* p, const void* spec, int layout, int kind, const d
                         fbi_bin_power_f64(p, spec, layout, kind, params, table_dev, p->scratch, s));
     if (r) return r;
     std::vector<double> h((size_t)2 * p->nbins);
-    FB_HIP(hipMemcpyAsync(h.data(), p->scratch, h.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    FB_HIP(hipStreamSynchronize(s));
+    FB_TRY(fb_read_back(h.data(), p->scratch, h.size() * sizeof(double), s));
     for (int q = 0; q < p->nbins; ++q) {
         count[q] = p->counts_host[q];
         sum[q] = h[(size_t)2 * q];
@@ -488,29 +479,22 @@ int bin_separation(fb_plan* p, const void* real, const double* edges, int nbins,
     const int nl = lmax / 2 + 1;
     const double elast = edges[nbins];
     std::vector<double> key(edges, edges + nbins + 1);
-    if (!p->sep_edges) FB_HIP(hipMalloc((void**)&p->sep_edges, (FB_MAX_SEP_BINS + 1) * sizeof(double)));
+    FB_TRY(p->sep_edges.ensure((FB_MAX_SEP_BINS + 1) * sizeof(double)));
     FB_HIP(hipMemcpyAsync(p->sep_edges, key.data(), key.size() * sizeof(double), hipMemcpyHostToDevice, s));
-    const std::vector<double>* geo = nullptr;
-    for (const auto& e : p->sep_geom)
-        if (e.size() == 3 * (size_t)nbins + 1 && std::equal(key.begin(), key.end(), e.begin())) geo = &e;
+    const std::vector<double>* geo = p->sep_geom.find(key);
     if (!geo) {                    // cells and sum |s| per bin: data independent, once per bin set
         int r = FB_DISPATCH(p, fbi_sep_bin_f32(p, nullptr, p->sep_edges, elast, nbins, nl, 1, p->scratch, s),
                             fbi_sep_bin_f64(p, nullptr, p->sep_edges, elast, nbins, nl, 1, p->scratch, s));
         if (r) return r;
-        std::vector<double> e(key);
-        e.resize(3 * (size_t)nbins + 1);
-        FB_HIP(hipMemcpyAsync(e.data() + nbins + 1, p->scratch, 2 * (size_t)nbins * sizeof(double), hipMemcpyDeviceToHost, s));
-        FB_HIP(hipStreamSynchronize(s));
-        if (p->sep_geom.size() >= 16) p->sep_geom.erase(p->sep_geom.begin());
-        p->sep_geom.push_back(std::move(e));
-        geo = &p->sep_geom.back();
+        std::vector<double> g(2 * (size_t)nbins);
+        FB_TRY(fb_read_back(g.data(), p->scratch, g.size() * sizeof(double), s));
+        geo = p->sep_geom.insert(key, std::move(g));
     }
     int r = FB_DISPATCH(p, fbi_sep_bin_f32(p, real, p->sep_edges, elast, nbins, nl, 0, p->scratch, s),
                         fbi_sep_bin_f64(p, real, p->sep_edges, elast, nbins, nl, 0, p->scratch, s));
     if (r) return r;
-    FB_HIP(hipMemcpyAsync(out_host + 2 * nbins, p->scratch, (size_t)nl * nbins * sizeof(double), hipMemcpyDeviceToHost, s));
-    FB_HIP(hipStreamSynchronize(s));
-    std::copy(geo->begin() + nbins + 1, geo->end(), out_host);
+    FB_TRY(fb_read_back(out_host + 2 * nbins, p->scratch, (size_t)nl * nbins * sizeof(double), s));   // (`key` has been read, too)
+    std::copy(geo->begin(), geo->end(), out_host);
     return FB_OK;
 }
 }  // namespace
@@ -910,9 +894,7 @@ int fb_memcpy_h2d(void* dst, const void* src, size_t bytes, void* stream) {
     return FB_OK;
 }
 int fb_memcpy_d2h(void* dst, const void* src, size_t bytes, void* stream) {
-    FB_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, (hipStream_t)stream));
-    FB_HIP(hipStreamSynchronize((hipStream_t)stream));
-    return FB_OK;
+    return fb_read_back(dst, src, bytes, (hipStream_t)stream);
 }
 int fb_memcpy_d2d(void* dst, const void* src, size_t bytes, void* stream) {
     FB_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));

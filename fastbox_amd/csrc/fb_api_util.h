@@ -6,6 +6,13 @@
 // HIP runtime may have left in this thread, so that the launch checks below report this call's errors only)
 #define FB_REQUIRE(cond, msg) do { (void)hipGetLastError(); if (!(cond)) { fb_set_error(msg); return FB_ERR_INVALID; } } while (0)
 #define FB_DISPATCH(p, call32, call64) ((p)->prec == 4 ? (call32) : (call64))
+// A few words of a result to the host, complete on return: the copy and the wait for stream s -- so everything queued on s
+// before it has finished as well, which callers rely on (see the comments where they call it).
+static inline int fb_read_back(void* host_dst, const void* dev_src, size_t bytes, hipStream_t s) {
+    FB_HIP(hipMemcpyAsync(host_dst, dev_src, bytes, hipMemcpyDeviceToHost, s));
+    FB_HIP(hipStreamSynchronize(s));
+    return FB_OK;
+}
 // A plan belongs to one device.  Every entry point that takes a plan makes that device current for the duration of the
 // call (allocations, NULL-stream launches and the plan's own auxiliary stream / events all follow the current device)
 // and puts the caller's device back when it returns -- other users of the HIP runtime in this thread (torch, RCCL)

@@ -271,9 +271,9 @@ int bispectrum(fb_plan* p, const void* real, void* work_half, void* work_shells,
     const size_t half_bytes = (size_t)rows * p->NZP * 2 * p->prec, real_bytes = (size_t)nvox * p->prec;
     const size_t split_need = (size_t)std::max(1LL, std::min((rows + 3) / 4, 4LL * p->num_cu)) * 3 * FB_BK_SPLIT;
     const size_t con_need = (size_t)bk_contract_blocks(p, (nvox + FB_BK_RUN - 1) / FB_BK_RUN, nb) * (nb <= 16 ? 16 : 64) * 256;
-    int r = ensure_bytes(&p->pca_work, &p->pca_work_cap, std::max(split_need, con_need) * sizeof(double));
+    int r = p->work.ensure(std::max(split_need, con_need) * sizeof(double));
     if (r) return r;
-    double* partial = (double*)p->pca_work;
+    double* partial = p->work.as<double>();
     if (!unit) {
         r = FB_DISPATCH(p, fbi_fft_r2c_f32(p, real, work_half, 0, s), fbi_fft_r2c_f64(p, real, work_half, 0, s));
         if (r) return r;
@@ -300,8 +300,7 @@ int bispectrum(fb_plan* p, const void* real, void* work_half, void* work_shells,
                     bk_contract_launch<double>(p, cubes, nb, partial, p->scratch, s));
     if (r) return r;
     std::vector<double> rec((size_t)T3 + 3 * nb);
-    FB_HIP(hipMemcpyAsync(rec.data(), p->scratch, rec.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    FB_HIP(hipStreamSynchronize(s));
+    FB_TRY(fb_read_back(rec.data(), p->scratch, rec.size() * sizeof(double), s));
     std::copy(rec.begin(), rec.begin() + T3, out_host);
     for (int b0 = 0; b0 < nb; b0 += nwork) {
         const int nq = std::min(nwork, nb - b0);

@@ -399,7 +399,6 @@ __global__ __launch_bounds__(256) void k_rotate_spectra(const T* __restrict__ cu
 }
 
 // ---- launchers ----------------------------------------------------------------------------------------------------------------
-int ensure_work(fb_plan* p, size_t bytes) { return ensure_bytes(&p->pca_work, &p->pca_work_cap, bytes); }
 int red_blocks(long long n) {
     const long long b = (n + 255) / 256;
     return (int)(b < FB_CLEAN_RED_BLOCKS ? (b < 1 ? 1 : b) : FB_CLEAN_RED_BLOCKS);
@@ -423,9 +422,8 @@ int nmf_sweep(fb_plan* p, const void* cube, double* W, double* H, int k, double*
     const size_t m = (size_t)N * k + (size_t)k * k + 1;
     // work: [H H^T: 256 | finished sums: m | violations: 2 | partials: nb m]
     const size_t head = 256 + m + 2;
-    int r = ensure_work(p, (head + (size_t)nb * m) * sizeof(double));
-    if (r) return r;
-    double* hht = (double*)p->pca_work;
+    FB_TRY(p->work.ensure((head + (size_t)nb * m) * sizeof(double)));
+    double* hht = p->work.as<double>();
     double* sums = hht + 256;
     double* viol = sums + m;
     double* partial = viol + 2;
@@ -447,8 +445,7 @@ int nmf_sweep(fb_plan* p, const void* cube, double* W, double* H, int k, double*
     sum_rows(partial, (int)nb, (long long)m, 1.0, sums, s);
     hipLaunchKernelGGL(k_nmf_update_h, dim3(1), dim3(256), 0, s, H, (const double*)sums, k, N, viol);
     FB_LAUNCH_CHECK("k_nmf_update_h");
-    FB_HIP(hipMemcpyAsync(viol_host, viol, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-    FB_HIP(hipStreamSynchronize(s));
+    FB_TRY(fb_read_back(viol_host, viol, 2 * sizeof(double), s));
     return FB_OK;
 }
 
@@ -459,9 +456,8 @@ int nmf_residual(fb_plan* p, const void* cube, const double* W, const double* H,
     const long long npix = (long long)N * N;
     long long nb = (npix + 3) / 4;
     if (nb > 2048) nb = 2048;
-    int r = ensure_work(p, (size_t)(nb + 1) * sizeof(double));
-    if (r) return r;
-    double* partial = (double*)p->pca_work + 1;
+    FB_TRY(p->work.ensure((size_t)(nb + 1) * sizeof(double)));
+    double* partial = p->work.as<double>() + 1;
     { FbProfScope _ps(p, FBK_PCA, s);
 #define FB_RES_CASE(C_)                                                                                                    \
     hipLaunchKernelGGL((k_nmf_residual<T, C_>), dim3((unsigned)nb), dim3(256), 0, s, (const T*)cube, W, H, k, npix, N,    \
@@ -479,10 +475,9 @@ int nmf_residual(fb_plan* p, const void* cube, const double* W, const double* H,
     }
     FB_LAUNCH_CHECK("k_nmf_residual");
     if (sumsq_host) {
-        sum_rows(partial, (int)nb, 1, 1.0, (double*)p->pca_work, s);
+        sum_rows(partial, (int)nb, 1, 1.0, p->work.as<double>(), s);
         FB_LAUNCH_CHECK("k_sum_rows");
-        FB_HIP(hipMemcpyAsync(sumsq_host, p->pca_work, sizeof(double), hipMemcpyDeviceToHost, s));
-        FB_HIP(hipStreamSynchronize(s));
+        FB_TRY(fb_read_back(sumsq_host, p->work, sizeof(double), s));
     }
     return FB_OK;
 }
@@ -513,15 +508,13 @@ template <typename T>
 int real_min(fb_plan* p, const void* x, double* out_host, hipStream_t s) {
     const long long n = (long long)p->N * p->N * p->N;
     const int nb = red_blocks(n);
-    int r = ensure_work(p, (size_t)(2 * nb + 2) * sizeof(double));
-    if (r) return r;
-    double* res = (double*)p->pca_work;
+    FB_TRY(p->work.ensure((size_t)(2 * nb + 2) * sizeof(double)));
+    double* res = p->work.as<double>();
     FbProfScope _ps(p, FBK_REALOP, s);
     hipLaunchKernelGGL((k_min_finite<T>), dim3(nb), dim3(256), 0, s, (const T*)x, n, res + 2);
     hipLaunchKernelGGL(k_min_finish, dim3(1), dim3(64), 0, s, (const double*)(res + 2), nb, res);
     FB_LAUNCH_CHECK("k_min_finite");
-    FB_HIP(hipMemcpyAsync(out_host, res, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-    FB_HIP(hipStreamSynchronize(s));
+    FB_TRY(fb_read_back(out_host, res, 2 * sizeof(double), s));
     return FB_OK;
 }
 
@@ -591,15 +584,13 @@ int fb_nndsvd_norms(fb_plan* p, const double* amps_dev, int k, double* out, void
     hipStream_t s = (hipStream_t)stream;
     const long long npix = (long long)p->N * p->N;
     const int nb = red_blocks(npix);
-    int r = ensure_work(p, (size_t)(nb + 1) * 2 * k * sizeof(double));
-    if (r) return r;
-    double* res = (double*)p->pca_work;
+    FB_TRY(p->work.ensure((size_t)(nb + 1) * 2 * k * sizeof(double)));
+    double* res = p->work.as<double>();
     { FbProfScope _ps(p, FBK_PCA, s);
     hipLaunchKernelGGL(k_rows_posneg, dim3(nb), dim3(256), 0, s, amps_dev, k, npix, res + 2 * k);
     sum_rows(res + 2 * k, nb, 2 * k, 1.0, res, s); }
     FB_LAUNCH_CHECK("k_rows_posneg");
-    FB_HIP(hipMemcpyAsync(out, res, (size_t)2 * k * sizeof(double), hipMemcpyDeviceToHost, s));
-    FB_HIP(hipStreamSynchronize(s));
+    FB_TRY(fb_read_back(out, res, (size_t)2 * k * sizeof(double), s));
     return FB_OK;
 }
 
@@ -609,13 +600,12 @@ int fb_nndsvd_fill(fb_plan* p, double* amps_dev, int k, const double* coef, int 
     FB_USE_DEVICE(p);
     hipStream_t s = (hipStream_t)stream;
     const long long npix = (long long)p->N * p->N;
-    int r = ensure_work(p, FB_CLEAN_KMAX * sizeof(double));
-    if (r) return r;
-    FB_HIP(hipMemcpyAsync(p->pca_work, coef, (size_t)k * sizeof(double), hipMemcpyHostToDevice, s));
+    FB_TRY(p->work.ensure(FB_CLEAN_KMAX * sizeof(double)));
+    FB_HIP(hipMemcpyAsync(p->work, coef, (size_t)k * sizeof(double), hipMemcpyHostToDevice, s));
     FB_HIP(hipStreamSynchronize(s));                               // `coef` is the caller's
     FbProfScope _ps(p, FBK_PCA, s);
     hipLaunchKernelGGL(k_rows_rectify, dim3(red_blocks(k * npix)), dim3(256), 0, s, amps_dev, k, npix,
-                       (const double*)p->pca_work, abs_first, eps, fill);
+                       p->work.as<const double>(), abs_first, eps, fill);
     FB_LAUNCH_CHECK("k_rows_rectify");
     return FB_OK;
 }
@@ -632,9 +622,8 @@ int fb_ica_step(fb_plan* p, const double* W, const double* X1_dev, int n, int fu
     if (nb > FB_CLEAN_RED_BLOCKS) nb = FB_CLEAN_RED_BLOCKS;
     const int m = n * n + n;
     // work: [W: 256 | result: m | partials: nb m]
-    int r = ensure_work(p, (size_t)(256 + m + nb * m) * sizeof(double));
-    if (r) return r;
-    double* wdev = (double*)p->pca_work;
+    FB_TRY(p->work.ensure((size_t)(256 + m + nb * m) * sizeof(double)));
+    double* wdev = p->work.as<double>();
     double* res = wdev + 256;
     FB_HIP(hipMemcpyAsync(wdev, W, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice, s));
     { FbProfScope _ps(p, FBK_PCA, s);
@@ -642,8 +631,7 @@ int fb_ica_step(fb_plan* p, const double* W, const double* X1_dev, int n, int fu
     sum_rows(res + m, (int)nb, m, 1.0 / (double)npix, res, s); }
     FB_LAUNCH_CHECK("k_ica_step");
     double h[FB_CLEAN_KMAX * FB_CLEAN_KMAX + FB_CLEAN_KMAX];
-    FB_HIP(hipMemcpyAsync(h, res, (size_t)m * sizeof(double), hipMemcpyDeviceToHost, s));
-    FB_HIP(hipStreamSynchronize(s));
+    FB_TRY(fb_read_back(h, res, (size_t)m * sizeof(double), s));
     for (int i = 0; i < n * n; ++i) G_out[i] = h[i];
     for (int i = 0; i < n; ++i) gp_out[i] = h[n * n + i];
     return FB_OK;
@@ -658,9 +646,8 @@ int fb_ica_sources(fb_plan* p, const double* W, const double* scale, const doubl
     const long long npix = (long long)p->N * p->N;
     const int nb = red_blocks(npix);
     // work: [W: 256 | scale: 16 | result: 2 n | partials: nb 2 n]
-    int r = ensure_work(p, (size_t)(256 + 16 + 2 * n + (size_t)nb * 2 * n) * sizeof(double));
-    if (r) return r;
-    double* wdev = (double*)p->pca_work;
+    FB_TRY(p->work.ensure((size_t)(256 + 16 + 2 * n + (size_t)nb * 2 * n) * sizeof(double)));
+    double* wdev = p->work.as<double>();
     double* sdev = wdev + 256;
     double* res = sdev + 16;
     FB_HIP(hipMemcpyAsync(wdev, W, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice, s));
@@ -671,8 +658,7 @@ int fb_ica_sources(fb_plan* p, const double* W, const double* scale, const doubl
     sum_rows(res + 2 * n, nb, 2 * n, 1.0 / (double)npix, res, s); }
     FB_LAUNCH_CHECK("k_ica_sources");
     double h[2 * FB_CLEAN_KMAX];
-    FB_HIP(hipMemcpyAsync(h, res, (size_t)2 * n * sizeof(double), hipMemcpyDeviceToHost, s));
-    FB_HIP(hipStreamSynchronize(s));                               // also: W and scale are the caller's
+    FB_TRY(fb_read_back(h, res, (size_t)2 * n * sizeof(double), s));   // also: W and scale are the caller's
     if (moments_out) for (int i = 0; i < 2 * n; ++i) moments_out[i] = h[i];
     return FB_OK;
 }

@@ -14,26 +14,6 @@
 #include <limits>
 #include <vector>
 
-// One k_perp edge set's transverse rows (m_x, m_y), as i N + j, sorted by bin (ascending inside a bin): what both estimators
-// gather through.  A row lies in bin np.digitize(k_perp, edges) - 1 with k_perp = sqrt(k_x k_x + k_y k_y) formed on the host
-// exactly as numpy forms it; rows outside [edges[0], edges[nb]) are not listed.  skip0: the row m_perp = 0 is left out.
-struct fb_cyl_rows {
-    std::vector<double> key;             // edges[nb + 1], skip0
-    int nb = 0;
-    int* rows_dev = nullptr;             // [off[nb]]
-    std::vector<int> off;                // [nb + 1] first row of each bin
-    std::vector<double> sumk;            // [nb] sum of k_perp over the bin's rows
-    bool has0 = false;                   // the row m_perp = 0 is listed (in bin 0: k_perp = 0)
-};
-
-void fb_cyl_release(fb_plan* p) {
-    for (fb_cyl_rows* e : p->cyl_rows) {
-        if (e->rows_dev) (void)hipFree(e->rows_dev);
-        delete e;
-    }
-    p->cyl_rows.clear();
-}
-
 namespace fb {
 namespace {
 
@@ -41,7 +21,6 @@ namespace {
 #define FB_CYL_MAX_PAR 1025      // k_par bins: one per |m_z| of a 2048^3 box
 #define FB_MAPS_MAX_BINS 256     // k_perp bins of fb_transverse_gram
 #define FB_MAPS_MAX_N 1024
-#define FB_CYL_LISTS 8           // edge sets a plan keeps
 
 inline double host_sq2(double a, double b) {
 #pragma clang fp contract(off)
@@ -51,14 +30,7 @@ inline double host_sq2(double a, double b) {
 int cyl_rows_get(fb_plan* p, const double* edges, int nb, bool skip0, const fb_cyl_rows** out) {
     std::vector<double> key(edges, edges + nb + 1);
     key.push_back(skip0 ? 1.0 : 0.0);
-    for (size_t q = 0; q < p->cyl_rows.size(); ++q)
-        if (p->cyl_rows[q]->key == key) {
-            fb_cyl_rows* e = p->cyl_rows[q];
-            p->cyl_rows.erase(p->cyl_rows.begin() + q);
-            p->cyl_rows.push_back(e);
-            *out = e;
-            return FB_OK;
-        }
+    if ((*out = p->cyl_rows.find(key))) return FB_OK;
     const int N = p->N;
     double kf[3];
     fill_kf(p, kf);
@@ -82,21 +54,15 @@ int cyl_rows_get(fb_plan* p, const double* edges, int nb, bool skip0, const fb_c
     for (int b = 0; b < nb; ++b) off[b + 1] += off[b];
     std::vector<int> rows(std::max(off[nb], 1)), next(off.begin(), off.end() - 1);
     for (int r = 0; r < N * N; ++r) if (bin[r] >= 0) rows[next[bin[r]]++] = r;
-    fb_cyl_rows* e = new fb_cyl_rows;
-    e->key = key; e->nb = nb; e->off = off;
-    e->sumk.resize(nb);
-    for (int b = 0; b < nb; ++b) e->sumk[b] = (double)sk[b];
-    e->has0 = bin[0] >= 0;
-    if (hipMalloc((void**)&e->rows_dev, rows.size() * sizeof(int)) != hipSuccess) { delete e; return fb_hip_check(hipErrorOutOfMemory, "hipMalloc"); }
-    const hipError_t ce = hipMemcpy(e->rows_dev, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice);
-    if (ce != hipSuccess) { (void)hipFree(e->rows_dev); delete e; return fb_hip_check(ce, "hipMemcpy"); }
-    if (p->cyl_rows.size() >= FB_CYL_LISTS) {           // (every entry point synchronises: no launch still reads the oldest list)
-        (void)hipFree(p->cyl_rows.front()->rows_dev);
-        delete p->cyl_rows.front();
-        p->cyl_rows.erase(p->cyl_rows.begin());
-    }
-    p->cyl_rows.push_back(e);
-    *out = e;
+    fb_cyl_rows e;
+    e.nb = nb; e.off = off;
+    e.sumk.resize(nb);
+    for (int b = 0; b < nb; ++b) e.sumk[b] = (double)sk[b];
+    e.has0 = bin[0] >= 0;
+    FB_TRY(e.rows_dev.ensure(rows.size() * sizeof(int)));
+    FB_HIP(hipMemcpy(e.rows_dev, rows.data(), rows.size() * sizeof(int), hipMemcpyHostToDevice));
+    // (a full cache drops its oldest list here; every entry point synchronises: no launch still reads it)
+    *out = p->cyl_rows.insert(std::move(key), std::move(e));
     return FB_OK;
 }
 
@@ -213,9 +179,9 @@ int bin_power_cyl(fb_plan* p, const void* half1, const void* half2, const double
     std::vector<int> idx(tab);
     idx.insert(idx.end(), choff.begin(), choff.end());
     idx.insert(idx.end(), lr.begin(), lr.end());
-    r = ensure_bytes((void**)&p->cyl_idx, &p->cyl_idx_cap, idx.size() * sizeof(int));
-    if (!r) r = ensure_bytes((void**)&p->cyl_partials, &p->cyl_partials_cap, (size_t)std::max(nch, 1) * NZV * sizeof(double));
-    if (!r) r = ensure_bytes((void**)&p->cyl_tab, &p->cyl_tab_cap, (size_t)nperp * npar * sizeof(double));
+    r = p->cyl_idx.ensure(idx.size() * sizeof(int));
+    if (!r) r = p->cyl_partials.ensure((size_t)std::max(nch, 1) * NZV * sizeof(double));
+    if (!r) r = p->cyl_tab.ensure((size_t)nperp * npar * sizeof(double));
     if (r) return r;
     double* sums_dev = p->cyl_tab;                                     // [nperp][npar] sum P
     FB_HIP(hipMemcpyAsync(p->cyl_idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice, s));
@@ -234,7 +200,7 @@ int bin_power_cyl(fb_plan* p, const void* half1, const void* half2, const double
     const double n3 = (double)N * N * N;
     const double scale = (p->L[0] * p->L[1] * p->L[2]) / (n3 * n3);
     { FbProfScope _ps(p, FBK_BIN, s);
-    hipLaunchKernelGGL(k_cyl_finish, dim3(nperp), dim3(256), 0, s, (const double*)p->cyl_partials, p->cyl_idx + 3 * nch,
+    hipLaunchKernelGGL(k_cyl_finish, dim3(nperp), dim3(256), 0, s, p->cyl_partials.as<const double>(), p->cyl_idx + 3 * nch,
                        p->cyl_idx + 3 * nch + nperp + 1, NZV, N, npar, scale, sums_dev); }
     FB_LAUNCH_CHECK("k_cyl_finish");
     const size_t nc = (size_t)nperp * npar;
@@ -417,8 +383,8 @@ int transverse_gram(fb_plan* p, const void* full1, const void* full2, const doub
         out_host[nb + b] = e->sumk[b];
         inv[b] = modes > 0.0 ? norm / modes : std::numeric_limits<double>::quiet_NaN();
     }
-    r = ensure_bytes((void**)&p->cyl_idx, &p->cyl_idx_cap, idx.size() * sizeof(int));
-    if (!r) r = ensure_bytes((void**)&p->cyl_tab, &p->cyl_tab_cap, (size_t)nb * sizeof(double));
+    r = p->cyl_idx.ensure(idx.size() * sizeof(int));
+    if (!r) r = p->cyl_tab.ensure((size_t)nb * sizeof(double));
     if (r) return r;
     FB_HIP(hipMemcpyAsync(p->cyl_idx, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice, s));
     FB_HIP(hipMemcpyAsync(p->cyl_tab, inv.data(), inv.size() * sizeof(double), hipMemcpyHostToDevice, s));
@@ -432,7 +398,7 @@ int transverse_gram(fb_plan* p, const void* full1, const void* full2, const doub
     FB_LAUNCH_CHECK("k_maps_gram");
     { FbProfScope _ps(p, FBK_PCA, s);
     hipLaunchKernelGGL(k_maps_finish, dim3((N + 63) / 64, N, nb), dim3(64), 0, s, (const double*)work_dev, p->cyl_idx + 3 * nch,
-                       (const double*)p->cyl_tab, N, cross ? 0 : 1, cl_dev); }
+                       p->cyl_tab.as<const double>(), N, cross ? 0 : 1, cl_dev); }
     FB_LAUNCH_CHECK("k_maps_finish");
     FB_HIP(hipStreamSynchronize(s));
     return FB_OK;

@@ -128,40 +128,34 @@ int fb_leading_eigenvectors(fb_plan* p, const double* cov_dev, int nmodes, doubl
     if (nmodes == 0) return FB_OK;
     hipStream_t s = (hipStream_t)stream;
     const size_t nn = (size_t)n * n;
-    double* work = nullptr;
-    FB_HIP(hipMalloc(reinterpret_cast<void**>(&work), (4 * nn + 2) * sizeof(double)));
+    FB_TRY(p->eig_work.ensure((4 * nn + 2) * sizeof(double)));      // not the shared work buffer: cov_dev may lie in it
+    double* work = p->eig_work;
     double *A[2] = {work, work + nn}, *V[2] = {work + 2 * nn, work + 3 * nn}, *norms = work + 4 * nn;
-    int rc = FB_OK, cur = 0, sweeps = 0;
+    int cur = 0, sweeps = 0;
     double h[2] = {0.0, 0.0}, prev_off = -1.0;
-    auto fail = [&](int code, const char* msg) { fb_set_error(msg); rc = code; };
-    do {
-        hipLaunchKernelGGL(k_eig_init, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, s, cov_dev, A[0], V[0], n);
-        const dim3 grid((unsigned)((n / 2 + 127) / 128), (unsigned)n);
-        for (;;) {
-            hipLaunchKernelGGL(k_eig_norms, dim3(1), dim3(1024), 0, s, A[cur], n, norms);
-            if ((rc = fb_hip_check(hipGetLastError(), "k_eig_norms"))) break;
-            if ((rc = fb_hip_check(hipMemcpyAsync(h, norms, sizeof(h), hipMemcpyDeviceToHost, s), "hipMemcpyAsync"))) break;
-            if ((rc = fb_hip_check(hipStreamSynchronize(s), "hipStreamSynchronize"))) break;
-            if (!(h[1] == h[1]) || h[1] > 1.7e308) { fail(FB_ERR_INVALID, "the matrix has non-finite entries"); break; }
-            if (h[0] <= 1e-30 * h[1]) break;                       // off-diagonal norm below 1e-15 of the matrix norm (or a zero matrix)
-            // (at the rounding floor of a large matrix the norm stops falling: accept it there)
-            if (prev_off >= 0.0 && h[0] <= 1e-26 * h[1] && h[0] > 0.25 * prev_off) break;
-            prev_off = h[0];
-            if (sweeps >= 60) { fail(FB_ERR_STATE, "Jacobi iteration did not converge in 60 sweeps"); break; }
-            for (int r = 0; r < n - 1; ++r) {
-                hipLaunchKernelGGL(k_jacobi_round, grid, dim3(128), 0, s, A[cur], A[cur ^ 1], V[cur], V[cur ^ 1], n, r);
-                cur ^= 1;
-            }
-            if ((rc = fb_hip_check(hipGetLastError(), "k_jacobi_round"))) break;
-            ++sweeps;
+    hipLaunchKernelGGL(k_eig_init, dim3((unsigned)((nn + 255) / 256)), dim3(256), 0, s, cov_dev, A[0], V[0], n);
+    FB_LAUNCH_CHECK("k_eig_init");
+    const dim3 grid((unsigned)((n / 2 + 127) / 128), (unsigned)n);
+    for (;;) {
+        hipLaunchKernelGGL(k_eig_norms, dim3(1), dim3(1024), 0, s, A[cur], n, norms);
+        FB_LAUNCH_CHECK("k_eig_norms");
+        FB_TRY(fb_read_back(h, norms, sizeof(h), s));
+        if (!(h[1] == h[1]) || h[1] > 1.7e308) { fb_set_error("the matrix has non-finite entries"); return FB_ERR_INVALID; }
+        if (h[0] <= 1e-30 * h[1]) break;                       // off-diagonal norm below 1e-15 of the matrix norm (or a zero matrix)
+        // (at the rounding floor of a large matrix the norm stops falling: accept it there)
+        if (prev_off >= 0.0 && h[0] <= 1e-26 * h[1] && h[0] > 0.25 * prev_off) break;
+        prev_off = h[0];
+        if (sweeps >= 60) { fb_set_error("Jacobi iteration did not converge in 60 sweeps"); return FB_ERR_STATE; }
+        for (int r = 0; r < n - 1; ++r) {
+            hipLaunchKernelGGL(k_jacobi_round, grid, dim3(128), 0, s, A[cur], A[cur ^ 1], V[cur], V[cur ^ 1], n, r);
+            cur ^= 1;
         }
-        if (rc) break;
-        hipLaunchKernelGGL(k_eig_select, dim3((unsigned)n), dim3(256), 0, s, A[cur], V[cur], n, nmodes, vals_dev, modes_dev);
-        if ((rc = fb_hip_check(hipGetLastError(), "k_eig_select"))) break;
-        rc = fb_hip_check(hipStreamSynchronize(s), "hipStreamSynchronize");          // the work buffer is freed below
-    } while (0);
-    (void)hipStreamSynchronize(s);
-    (void)hipFree(work);
-    if (sweeps_out) *sweeps_out = sweeps;
-    return rc;
+        FB_LAUNCH_CHECK("k_jacobi_round");
+        ++sweeps;
+        if (sweeps_out) *sweeps_out = sweeps;
+    }
+    hipLaunchKernelGGL(k_eig_select, dim3((unsigned)n), dim3(256), 0, s, A[cur], V[cur], n, nmodes, vals_dev, modes_dev);
+    FB_LAUNCH_CHECK("k_eig_select");
+    FB_HIP(hipStreamSynchronize(s));              // the caller reads sweeps_out and the outputs
+    return FB_OK;
 }

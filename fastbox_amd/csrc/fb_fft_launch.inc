@@ -23,16 +23,11 @@ KGeom fft_geom(const fb_plan* p) { return KGeom{p->axis2, p->ksc, p->kpar, p->N,
 // which amplitude table the fused generator reads: the k_z-contiguous table when there is one (built from the
 // shell table of a cubic box, or given directly for any box shape), else the caller's dense per-mode table
 int gen_amplitude(const fb_plan* p, StridedOp<real_t>& op) {
-    op.amp.shell = (p->amp_dense || p->amp_sym_only) ? nullptr : reinterpret_cast<const real_t*>(p->amp_shell);
+    op.amp.shell = (p->amp_dense || p->amp_sym_only) ? nullptr : p->amp_shell.as<const real_t>();
     op.amp.dense = p->amp_sym_only ? nullptr : reinterpret_cast<const real_t*>(p->amp_dense);
-    op.amp.sym = (op.amp.shell || p->amp_sym_only) ? reinterpret_cast<const real_t*>(p->amp_sym) : nullptr;
+    op.amp.sym = (op.amp.shell || p->amp_sym_only) ? p->amp_sym.as<const real_t>() : nullptr;
     if (!op.amp.shell && !op.amp.dense && !op.amp.sym) { fb_set_error("amplitude table not set (fb_set_amplitude_*)"); return FB_ERR_STATE; }
     return FB_OK;
-}
-
-// room for `need` doubles in one of the plan's grow-only partials buffers
-int ensure(double** buf, size_t* cap, size_t need) {
-    return ensure_bytes(reinterpret_cast<void**>(buf), cap, need * sizeof(double));
 }
 
 // PERSIST: resident workgroups that walk the tiles (k_fft_strided); 0: one workgroup per tile.  BLK: slab addressing.
@@ -78,21 +73,21 @@ int launch_strided_npb(fb_plan* p, const StridedArgs<real_t>& a, int nouter, int
     }
     // (a chunk sequence that was never closed -- an exception or a failed collective between two fb_slab_x_bin_chunk calls --
     // must not turn a later whole-spectrum binning launch into an append: only launches over a tile range append)
-    if (smode_bins(MODE) && p->bin_append_cap && !a.ntx) p->bin_append_cap = 0;
-    if (smode_bins(MODE) && p->bin_append_cap) {
+    if (smode_bins(MODE) && p->bin_append_cols && !a.ntx) p->bin_append_cols = 0;
+    if (smode_bins(MODE) && p->bin_append_cols) {
         // one of several launches that share a table of partial sums (the k_z chunks of the slab-decomposed transform):
-        // this one's workgroups take the next nblk columns of a table of p->bin_append_cap (allocated by the caller)
-        if (p->bin_rows + nblk > p->bin_append_cap) { fb_set_error("binning chunks exceed the partial-sum table"); return FB_ERR_STATE; }
+        // this one's workgroups take the next nblk columns of a table of p->bin_append_cols (allocated by the caller)
+        if (p->bin_rows + nblk > p->bin_append_cols) { fb_set_error("binning chunks exceed the partial-sum table"); return FB_ERR_STATE; }
         op.partial = p->bin_partials + p->bin_rows;
-        op.partial_stride = p->bin_append_cap;
+        op.partial_stride = p->bin_append_cols;
         p->bin_rows += nblk;
         p->bin_rows_main = p->bin_rows;
     } else if (smode_bins(MODE)) {
         const long long rows = nblk + (a.packed ? N : 0);     // packed: one more column per k_y row (k_bin_packed_plane)
 #ifdef FB_STAMPS
-        r = ensure(&p->bin_partials, &p->bin_partials_cap, (size_t)rows * 2 * op.nbins + (size_t)nblk * 32 + 64);
+        r = p->bin_partials.ensure(((size_t)rows * 2 * op.nbins + (size_t)nblk * 32 + 64) * sizeof(double));
 #else
-        r = ensure(&p->bin_partials, &p->bin_partials_cap, (size_t)rows * 2 * op.nbins);
+        r = p->bin_partials.ensure((size_t)rows * 2 * op.nbins * sizeof(double));
 #endif
         if (r) return r;
         op.partial = p->bin_partials;
@@ -181,7 +176,7 @@ int launch_contig_n(fb_plan* p, ContigArgs<real_t>& a, int sign, hipStream_t s) 
     const long long nblk = (a.nlines + LPW - 1) / LPW;
     a.exp_shift = (real_t)p->exp_shift;
     if ((MODE == ZMODE_R2C || MODE == ZMODE_C2R2C) && a.pre_exp) {     // exp_base: blocks of earlier plane batches
-        r = ensure(&p->exp_partials, &p->exp_partials_cap, (size_t)(p->exp_base + nblk));
+        r = p->exp_partials.ensure((size_t)(p->exp_base + nblk) * sizeof(double));
         if (r) return r;
         a.exp_partial = p->exp_partials + p->exp_base;
         p->exp_rows = p->exp_base + nblk;
@@ -213,7 +208,7 @@ int launch_contig(fb_plan* p, int NF, ContigArgs<real_t>& a, int sign, hipStream
 template <int MODE>
 int launch_generic(fb_plan* p, GenericArgs<real_t>& a, int nouter, hipStream_t s) {
     if (!factor_smooth(a.n, a.rp)) { fb_set_error("unsupported grid size: nsamp must be even with prime factors 2, 3, 5 only"); return FB_ERR_UNSUPPORTED; }
-    a.tw = reinterpret_cast<const cplx_t*>(p->tw);
+    a.tw = p->tw.as<const cplx_t>();
     a.N = p->N;
     int TZ = (int)(65536 / ((size_t)2 * a.n * sizeof(cplx_t)));
     TZ = TZ < 1 ? 1 : (TZ > 8 ? 8 : TZ);
@@ -282,12 +277,12 @@ bool use_packed(const fb_plan* p) {
     return env != 0 && p->N >= 16;
 }
 StridedArgs<real_t> half_x(const fb_plan* p, cplx_t* h, bool packed = false) {
-    StridedArgs<real_t> a{h, h, (const cplx_t*)p->tw, (long long)p->NR * p->NZP, (long long)p->NZP, packed ? p->N / 2 : p->NZV, (real_t)1};
+    StridedArgs<real_t> a{h, h, p->tw.as<const cplx_t>(), (long long)p->NR * p->NZP, (long long)p->NZP, packed ? p->N / 2 : p->NZV, (real_t)1};
     a.packed = packed;
     return a;
 }
 StridedArgs<real_t> half_y(const fb_plan* p, cplx_t* h, bool packed = false) {
-    StridedArgs<real_t> a{h, h, (const cplx_t*)p->tw, (long long)p->NZP, (long long)p->NR * p->NZP, packed ? p->N / 2 : p->NZV, (real_t)1};
+    StridedArgs<real_t> a{h, h, p->tw.as<const cplx_t>(), (long long)p->NZP, (long long)p->NR * p->NZP, packed ? p->N / 2 : p->NZV, (real_t)1};
     a.packed = packed;
     return a;
 }
@@ -360,7 +355,7 @@ int yz_passes(fb_plan* p, cplx_t* h, const void* real_in, void* real_out, bool y
     const PlaneBatches pb = plane_batches(p, (size_t)hplane * sizeof(cplx_t) + (size_t)rplane * sizeof(real_t));
     int r = FB_OK;
     if (pre_exp && pb.count > 1) {       // one allocation for every batch's block sums (no reallocation mid-way)
-        r = ensure(&p->exp_partials, &p->exp_partials_cap, (size_t)rplane + (size_t)pb.count);
+        r = p->exp_partials.ensure(((size_t)rplane + (size_t)pb.count) * sizeof(double));
         if (r) return r;
     }
     r = fork_streams(p, pb, s);
@@ -373,11 +368,11 @@ int yz_passes(fb_plan* p, cplx_t* h, const void* real_in, void* real_out, bool y
         if (y_before) r = launch_plain(p, N, half_y(p, hb, packed), cnt, +1, st);
         if (r) break;
         if (ZM == ZMODE_R2C) {
-            ContigArgs<real_t> az{reinterpret_cast<const real_t*>(real_in) + p0 * rplane, hb, (const cplx_t*)p->tw, (long long)N,
+            ContigArgs<real_t> az{reinterpret_cast<const real_t*>(real_in) + p0 * rplane, hb, p->tw.as<const cplx_t>(), (long long)N,
                                   (long long)p->NZP, 0, N, cnt * (long long)N, (real_t)1, pre_exp, nullptr, nullptr, packed};
             r = launch_contig<ZM>(p, N / 2, az, -1, st);
         } else {
-            ContigArgs<real_t> az{hb, real_out ? reinterpret_cast<real_t*>(real_out) + p0 * rplane : nullptr, (const cplx_t*)p->tw, (long long)p->NZP,
+            ContigArgs<real_t> az{hb, real_out ? reinterpret_cast<real_t*>(real_out) + p0 * rplane : nullptr, p->tw.as<const cplx_t>(), (long long)p->NZP,
                                   (long long)N, N, 0, cnt * (long long)N, (real_t)scale, pre_exp, nullptr,
                                   ZM == ZMODE_C2R2C ? hb : nullptr, packed};
             r = launch_contig<ZM>(p, N / 2, az, +1, st);
@@ -399,7 +394,7 @@ int bin_x_pass(fb_plan* p, cplx_t* h, bool packed, int pre_exp, double* results,
     op.g = fft_geom(p);
     op.thr = p->thr; op.bins = p->bins; op.nbins = nb; op.namb = p->namb; op.store = 0;
     for (int q = 0; q < 8; ++q) op.amb[q] = p->amb[q];
-    op.plane_out = packed ? reinterpret_cast<cplx_t*>(p->plane_buf) : nullptr;
+    op.plane_out = packed ? p->plane_buf.as<cplx_t>() : nullptr;
     int r = launch_strided<SMODE_BIN>(p, N, half_x(p, h, packed), N, -1, op, s);
     if (r) return r;
     if (packed) {
@@ -408,7 +403,7 @@ int bin_x_pass(fb_plan* p, cplx_t* h, bool packed, int pre_exp, double* results,
         for (int q = 0; q < 8; ++q) bg.amb[q] = p->amb[q];
         const size_t lds = (size_t)nb * sizeof(double) + (size_t)8 * nb * sizeof(double) + (size_t)nb * sizeof(int);
         { FbProfScope _ps(p, FBK_BIN, s);
-        hipLaunchKernelGGL(k_bin_packed_plane<real_t>, dim3(N), dim3(256), lds, s, reinterpret_cast<const cplx_t*>(p->plane_buf),
+        hipLaunchKernelGGL(k_bin_packed_plane<real_t>, dim3(N), dim3(256), lds, s, p->plane_buf.as<const cplx_t>(),
                            op.g, bg, p->bin_partials, p->bin_rows, p->bin_rows_main); }
         FB_LAUNCH_CHECK("k_bin_packed_plane");
     }
@@ -478,7 +473,7 @@ int FB_CAT(fbi_fft_c2c_, FB_SUFFIX)(fb_plan* p, void* data, int sign, double sca
     const int N = p->N;
     const long long NN = (long long)N * N;
     cplx_t* d = reinterpret_cast<cplx_t*>(data);
-    const cplx_t* tw = reinterpret_cast<const cplx_t*>(p->tw);
+    const cplx_t* tw = p->tw.as<const cplx_t>();
     StridedArgs<real_t> ax{d, d, tw, NN, (long long)N, N, (real_t)1};
     int r = launch_plain(p, N, ax, N, sign, s);          // x lines, tiles over (y, z)
     if (r) return r;
@@ -510,7 +505,7 @@ int fft_axes01_nz(fb_plan* p, cplx_t* d, int nz, int sign, double scale, hipStre
                   int y_plane0 = 0, int y_planes = -1) {
     const int N = p->N;
     const long long plane = (long long)N * nz;
-    const cplx_t* tw = reinterpret_cast<const cplx_t*>(p->tw);
+    const cplx_t* tw = p->tw.as<const cplx_t>();
     if (y_planes < 0) y_planes = N;
     StridedArgs<real_t> ax{d, d, tw, plane, (long long)nz, nz, (real_t)1};
     cplx_t* dy = d + y_plane0 * plane;
@@ -578,7 +573,7 @@ int FB_CAT(fbi_fft2d_c2c_, FB_SUFFIX)(fb_plan* p, void* data, int sign, double s
         if (r) return r;
         return generic_strided(p, d, N, 0LL, N, 1, sign, 1.0, s);
     }
-    const cplx_t* tw = reinterpret_cast<const cplx_t*>(p->tw);
+    const cplx_t* tw = p->tw.as<const cplx_t>();
     ContigArgs<real_t> ay{d, d, tw, (long long)N, (long long)N, 0, 0, (long long)N, (real_t)scale, 0, nullptr, nullptr};
     int r = launch_contig<ZMODE_C2C>(p, N, ay, sign, s);
     if (r) return r;
@@ -778,7 +773,7 @@ int FB_CAT(fbi_power_redshift_space_, FB_SUFFIX)(fb_plan* p, void* work_d, void*
         a.in_d = hd + p0 * hplane; a.in_v = hv + p0 * hplane;
         a.dx_out = real_d_out ? reinterpret_cast<real_t*>(real_d_out) + p0 * rplane : nullptr;
         a.out = ho + p0 * hplane;
-        a.tw = (const cplx_t*)p->tw; a.zgrid = p->zgrid; a.pitch = p->NZP;
+        a.tw = p->tw.as<const cplx_t>(); a.zgrid = p->zgrid; a.pitch = p->NZP;
         a.nlines = cnt * (long long)N; a.line0 = p0 * (long long)N;
         a.scale_d = (real_t)scale; a.scale_v = (real_t)scale; a.packed_in = packed ? 1 : 0;
         a.Hz = Hz; a.sigma_nl = sigma_nl;
@@ -813,13 +808,13 @@ int FB_CAT(fbi_debug_pass_, FB_SUFFIX)(fb_plan* p, void* half, int axis, int mod
     mode %= 10;
     struct Reset { fb_plan* q; ~Reset() { q->debug_no_mem = 0; } } reset{p};
     if (mode == 1) {
-        op.amp.shell = reinterpret_cast<const real_t*>(p->amp_shell);
+        op.amp.shell = p->amp_shell.as<const real_t>();
         op.amp.dense = nullptr;
-        op.amp.sym = reinterpret_cast<const real_t*>(p->amp_sym);
+        op.amp.sym = p->amp_sym.as<const real_t>();
         if (!op.amp.shell) { fb_set_error("amplitude shells not set"); return FB_ERR_STATE; }
 #ifdef FB_STAMPS
         {
-            int r = ensure(&p->bin_partials, &p->bin_partials_cap, (size_t)N * 64 * 32 + 4096);
+            int r = p->bin_partials.ensure(((size_t)N * 64 * 32 + 4096) * sizeof(double));
             if (r) return r;
             op.bins = p->bin_partials;          // time stamps (the generator does not read bins)
         }
@@ -834,7 +829,7 @@ int FB_CAT(fbi_debug_pass_, FB_SUFFIX)(fb_plan* p, void* half, int axis, int mod
     }
 #ifdef FB_STAMPS
     {   // diagnostic build: time stamps land in bin_partials (8 int64 per workgroup)
-        int r = ensure(&p->bin_partials, &p->bin_partials_cap, (size_t)N * 64 * 32 + 4096);
+        int r = p->bin_partials.ensure(((size_t)N * 64 * 32 + 4096) * sizeof(double));
         if (r) return r;
         op.bins = p->bin_partials;
         return launch_strided<SMODE_PLAIN>(p, N, a, N, -1, op, s);
@@ -847,10 +842,10 @@ int FB_CAT(fbi_debug_pass_, FB_SUFFIX)(fb_plan* p, void* half, int axis, int mod
 // ---- slab-decomposed 3-D FFT (one x-slab / k_y-slab per rank; the exchange is done by the host) ------
 namespace {
 StridedArgs<real_t> slab_y(const fb_plan* p, cplx_t* h) {       // x-slab [nxl][NR][NZP]: y lines
-    return StridedArgs<real_t>{h, h, (const cplx_t*)p->tw, (long long)p->NZP, (long long)p->NR * p->NZP, p->NZV, (real_t)1};
+    return StridedArgs<real_t>{h, h, p->tw.as<const cplx_t>(), (long long)p->NZP, (long long)p->NR * p->NZP, p->NZV, (real_t)1};
 }
 StridedArgs<real_t> slab_x(const fb_plan* p, cplx_t* k, int nyl) {  // k-space slab [N][nyl][NZP]: x lines
-    return StridedArgs<real_t>{k, k, (const cplx_t*)p->tw, (long long)nyl * p->NZP, (long long)p->NZP, p->NZV, (real_t)1};
+    return StridedArgs<real_t>{k, k, p->tw.as<const cplx_t>(), (long long)nyl * p->NZP, (long long)p->NZP, p->NZV, (real_t)1};
 }
 }  // namespace
 
@@ -858,7 +853,7 @@ int FB_CAT(fbi_slab_forward_local_, FB_SUFFIX)(fb_plan* p, const void* real_loca
                                                int pre_exp, double* expsum, hipStream_t s) {
     const int N = p->N;
     cplx_t* h = reinterpret_cast<cplx_t*>(half_local);
-    ContigArgs<real_t> az{real_local, h, (const cplx_t*)p->tw, (long long)N, (long long)p->NZP, 0, N,
+    ContigArgs<real_t> az{real_local, h, p->tw.as<const cplx_t>(), (long long)N, (long long)p->NZP, 0, N,
                           (long long)nxl * N, (real_t)1, pre_exp, nullptr, nullptr};
     int r = launch_contig<ZMODE_R2C>(p, N / 2, az, -1, s);
     if (r) return r;
@@ -876,7 +871,7 @@ int FB_CAT(fbi_slab_inverse_local_, FB_SUFFIX)(fb_plan* p, void* half_local, voi
     cplx_t* h = reinterpret_cast<cplx_t*>(half_local);
     int r = launch_plain(p, N, slab_y(p, h), nxl, +1, s);
     if (r) return r;
-    ContigArgs<real_t> az{h, real_local, (const cplx_t*)p->tw, (long long)p->NZP, (long long)N, N, 0,
+    ContigArgs<real_t> az{h, real_local, p->tw.as<const cplx_t>(), (long long)p->NZP, (long long)N, N, 0,
                           (long long)nxl * N, (real_t)scale, 0, nullptr, nullptr};
     return launch_contig<ZMODE_C2R>(p, N / 2, az, +1, s);
 }
@@ -902,7 +897,7 @@ int FB_CAT(fbi_slab_forward_packed_, FB_SUFFIX)(fb_plan* p, const void* real_loc
                                                 int nxl, int nparts, int pre_exp, double* expsum, hipStream_t s) {
     const int N = p->N;
     cplx_t* h = reinterpret_cast<cplx_t*>(half_local);
-    ContigArgs<real_t> az{real_local, h, (const cplx_t*)p->tw, (long long)N, (long long)p->NZP, 0, N,
+    ContigArgs<real_t> az{real_local, h, p->tw.as<const cplx_t>(), (long long)N, (long long)p->NZP, 0, N,
                           (long long)nxl * N, (real_t)1, pre_exp, nullptr, nullptr};
     int r = launch_contig<ZMODE_R2C>(p, N / 2, az, -1, s);
     if (r) return r;
@@ -928,7 +923,7 @@ int FB_CAT(fbi_slab_inverse_packed_, FB_SUFFIX)(fb_plan* p, const void* xbuf, vo
     if (r) return r;
     r = launch_plain(p, N, ay, nxl, +1, s);
     if (r) return r;
-    ContigArgs<real_t> az{h, real_local, (const cplx_t*)p->tw, (long long)p->NZP, (long long)N, N, 0,
+    ContigArgs<real_t> az{h, real_local, p->tw.as<const cplx_t>(), (long long)p->NZP, (long long)N, N, 0,
                           (long long)nxl * N, (real_t)scale, 0, nullptr, nullptr};
     return launch_contig<ZMODE_C2R>(p, N / 2, az, +1, s);
 }
@@ -947,7 +942,7 @@ int FB_CAT(fbi_slab_turnaround_, FB_SUFFIX)(fb_plan* p, const void* recvbuf, voi
     if (r) return r;
     r = launch_plain(p, N, ai, nxl, +1, s);
     if (r) return r;
-    ContigArgs<real_t> az{h, real_local, (const cplx_t*)p->tw, (long long)p->NZP, (long long)N, N, 0,
+    ContigArgs<real_t> az{h, real_local, p->tw.as<const cplx_t>(), (long long)p->NZP, (long long)N, N, 0,
                           (long long)nxl * N, (real_t)scale, pre_exp, nullptr, h};
     r = launch_contig<ZMODE_C2R2C>(p, N / 2, az, +1, s);
     if (r) return r;
@@ -971,9 +966,9 @@ int FB_CAT(fbi_slab_x_generate_, FB_SUFFIX)(fb_plan* p, void* kslab, int nyl, in
                                             hipStream_t s) {
     StridedOp<real_t> op = {};
     op.g = fft_geom(p);
-    op.amp.shell = reinterpret_cast<const real_t*>(p->amp_shell);
+    op.amp.shell = p->amp_shell.as<const real_t>();
     if (!op.amp.shell || p->amp_dense) { fb_set_error("slab generation needs shell amplitudes (cubic box)"); return FB_ERR_STATE; }
-    op.amp.sym = reinterpret_cast<const real_t*>(p->amp_sym);
+    op.amp.sym = p->amp_sym.as<const real_t>();
     op.key.k[0] = (uint32_t)seed; op.key.k[1] = (uint32_t)(seed >> 32);
     op.key.k[2] = (uint32_t)real; op.key.k[3] = (uint32_t)(real >> 32);
     op.outer0 = ky0;
@@ -1032,14 +1027,14 @@ int FB_CAT(fbi_slab_x_generate_chunk_, FB_SUFFIX)(fb_plan* p, void* kchunk, int 
     const long long W = (long long)ntile * TZ;
     StridedOp<real_t> op = {};
     op.g = fft_geom(p);
-    op.amp.shell = reinterpret_cast<const real_t*>(p->amp_shell);
+    op.amp.shell = p->amp_shell.as<const real_t>();
     if (!op.amp.shell || p->amp_dense) { fb_set_error("slab generation needs shell amplitudes (cubic box)"); return FB_ERR_STATE; }
-    op.amp.sym = reinterpret_cast<const real_t*>(p->amp_sym);
+    op.amp.sym = p->amp_sym.as<const real_t>();
     op.key.k[0] = (uint32_t)seed; op.key.k[1] = (uint32_t)(seed >> 32);
     op.key.k[2] = (uint32_t)real; op.key.k[3] = (uint32_t)(real >> 32);
     op.outer0 = ky0;
     cplx_t* k = reinterpret_cast<cplx_t*>(kchunk) - (long long)tile0 * TZ;       // columns are addressed absolutely
-    StridedArgs<real_t> a{k, k, (const cplx_t*)p->tw, (long long)nyl * W, W, p->NZV, (real_t)1};
+    StridedArgs<real_t> a{k, k, p->tw.as<const cplx_t>(), (long long)nyl * W, W, p->NZV, (real_t)1};
     a.ntx = ntile; a.tile0 = tile0;
     return launch_strided<SMODE_GEN>(p, p->N, a, nyl, +1, op, s);
 }
@@ -1078,15 +1073,15 @@ int FB_CAT(fbi_slab_z_pass_, FB_SUFFIX)(fb_plan* p, void* half_local, void* real
     cplx_t* h = reinterpret_cast<cplx_t*>(half_local);
     int r;
     if (which == 1) {
-        ContigArgs<real_t> az{real_local, h, (const cplx_t*)p->tw, (long long)N, (long long)p->NZP, 0, N,
+        ContigArgs<real_t> az{real_local, h, p->tw.as<const cplx_t>(), (long long)N, (long long)p->NZP, 0, N,
                               (long long)nxl * N, (real_t)1, pre_exp, nullptr, nullptr};
         r = launch_contig<ZMODE_R2C>(p, N / 2, az, -1, s);
     } else if (which == 2) {
-        ContigArgs<real_t> az{h, real_local, (const cplx_t*)p->tw, (long long)p->NZP, (long long)N, N, 0,
+        ContigArgs<real_t> az{h, real_local, p->tw.as<const cplx_t>(), (long long)p->NZP, (long long)N, N, 0,
                               (long long)nxl * N, (real_t)scale, pre_exp, nullptr, h};
         r = launch_contig<ZMODE_C2R2C>(p, N / 2, az, +1, s);
     } else {
-        ContigArgs<real_t> az{h, real_local, (const cplx_t*)p->tw, (long long)p->NZP, (long long)N, N, 0,
+        ContigArgs<real_t> az{h, real_local, p->tw.as<const cplx_t>(), (long long)p->NZP, (long long)N, N, 0,
                               (long long)nxl * N, (real_t)scale, 0, nullptr, nullptr};
         r = launch_contig<ZMODE_C2R>(p, N / 2, az, +1, s);
     }
@@ -1108,24 +1103,24 @@ int FB_CAT(fbi_slab_x_bin_chunk_, FB_SUFFIX)(fb_plan* p, void* kchunk, int nyl, 
     const long long W = (long long)ntile * TZ;
     if (first) {
         const long long cap = (long long)((p->NZP + TZ - 1) / TZ) * nyl;      // one column per tile of the whole slab
-        int r = ensure(&p->bin_partials, &p->bin_partials_cap, (size_t)cap * 2 * nb);
+        int r = p->bin_partials.ensure((size_t)cap * 2 * nb * sizeof(double));
         if (r) return r;
-        p->bin_append_cap = cap;
+        p->bin_append_cols = cap;
         p->bin_rows = 0;
     }
-    if (!p->bin_append_cap) { fb_set_error("fb_slab_x_bin_chunk: no chunk sequence open (first = 1)"); return FB_ERR_STATE; }
+    if (!p->bin_append_cols) { fb_set_error("fb_slab_x_bin_chunk: no chunk sequence open (first = 1)"); return FB_ERR_STATE; }
     StridedOp<real_t> op = {};
     op.g = fft_geom(p);
     op.thr = p->thr; op.bins = p->bins; op.nbins = nb; op.namb = p->namb; op.store = 0; op.outer0 = ky0;
     for (int q = 0; q < 8; ++q) op.amb[q] = p->amb[q];
     cplx_t* k = reinterpret_cast<cplx_t*>(kchunk) - (long long)tile0 * TZ;
-    StridedArgs<real_t> a{k, k, (const cplx_t*)p->tw, (long long)nyl * W, W, p->NZV, (real_t)1};
+    StridedArgs<real_t> a{k, k, p->tw.as<const cplx_t>(), (long long)nyl * W, W, p->NZV, (real_t)1};
     a.ntx = ntile; a.tile0 = tile0;
     int r = launch_strided<SMODE_BIN>(p, p->N, a, nyl, -1, op, s);
-    if (r) { p->bin_append_cap = 0; return r; }
+    if (r) { p->bin_append_cols = 0; return r; }
     if (last) {
-        const long long rows = p->bin_rows, cap = p->bin_append_cap;
-        p->bin_append_cap = 0;
+        const long long rows = p->bin_rows, cap = p->bin_append_cols;
+        p->bin_append_cols = 0;
         { FbProfScope _ps(p, FBK_BIN, s);
         hipLaunchKernelGGL(k_sum_columns, dim3(2 * nb), dim3(256), 0, s, p->bin_partials, rows, 2 * nb, results, (const double*)nullptr, 0LL, cap); }
         FB_LAUNCH_CHECK("k_sum_columns");

@@ -3,6 +3,7 @@
 #include <cmath>
 #include <cstdlib>
 #include "fb_plan.h"
+#include "fb_api_util.h"
 #include "fb_field_kernels.h"
 #include <vector>
 
@@ -35,9 +36,9 @@ int mode_block(int nz) {                 // threads along k_z: least padding (N/
 }
 
 int amp_src(const fb_plan* p, AmpSrc<real_t>& a) {
-    a.shell = reinterpret_cast<const real_t*>(p->amp_shell);
+    a.shell = p->amp_shell.as<const real_t>();
     a.dense = reinterpret_cast<const real_t*>(p->amp_dense);
-    a.sym = reinterpret_cast<const real_t*>(p->amp_sym);
+    a.sym = p->amp_sym.as<const real_t>();
     if (a.dense) a.shell = nullptr;
     if (p->amp_sym_only) { a.shell = nullptr; a.dense = nullptr; }
     if (!a.shell && !a.dense && !a.sym) { fb_set_error("amplitude table not set (fb_set_amplitude_*)"); return FB_ERR_STATE; }
@@ -52,21 +53,20 @@ int amp_src(const fb_plan* p, AmpSrc<real_t>& a) {
 int FBI(set_amp_shells)(fb_plan* p, const double* amp, int64_t n) {
     std::vector<real_t> tmp((size_t)n);
     for (int64_t q = 0; q < n; ++q) tmp[(size_t)q] = (real_t)amp[q];
-    if (p->amp_shell) { FB_HIP(hipFree(p->amp_shell)); p->amp_shell = nullptr; }
-    FB_HIP(hipMalloc(&p->amp_shell, (size_t)n * sizeof(real_t)));
+    FB_TRY(p->amp_shell.reset());
+    FB_TRY(p->amp_shell.ensure((size_t)n * sizeof(real_t)));
     FB_HIP(hipMemcpy(p->amp_shell, tmp.data(), (size_t)n * sizeof(real_t), hipMemcpyHostToDevice));
     p->nshell = n;
     p->amp_sym_only = 0;
     // the generator's k_z-contiguous copy (see k_build_amp_sym); FB_NO_AMP_SYM=1 keeps only the shell table
     const int N = p->N, M = N / 2 + 1;
     if (const char* e = getenv("FB_NO_AMP_SYM")) if (e[0] == '1') {
-        if (p->amp_sym) { FB_HIP(hipFree(p->amp_sym)); p->amp_sym = nullptr; }
-        return FB_OK;
+        return p->amp_sym.reset();
     }
     if (n < (int64_t)3 * (N / 2) * (N / 2) + 1) { fb_set_error("shell table shorter than 3 (N/2)^2 + 1"); return FB_ERR_INVALID; }
-    if (!p->amp_sym) FB_HIP(hipMalloc(&p->amp_sym, (size_t)M * M * p->NZP * sizeof(real_t)));
+    FB_TRY(p->amp_sym.ensure((size_t)M * M * p->NZP * sizeof(real_t)));
     hipLaunchKernelGGL((k_build_amp_sym<real_t>), dim3((p->NZP + 63) / 64, M, M), dim3(64), 0, 0,
-                       (const real_t*)p->amp_shell, (real_t*)p->amp_sym, N, p->NZP);
+                       p->amp_shell.as<const real_t>(), p->amp_sym.as<real_t>(), N, p->NZP);
     FB_LAUNCH_CHECK("k_build_amp_sym");
     FB_HIP(hipDeviceSynchronize());
     return FB_OK;
@@ -82,7 +82,7 @@ int FBI(set_amp_sym)(fb_plan* p, const double* amp, int64_t n) {
         for (int b = 0; b < M; ++b)
             for (int c = 0; c < M; ++c)
                 tmp[((size_t)a * M + b) * p->NZP + c] = (real_t)amp[((size_t)a * M + b) * M + c];
-    if (!p->amp_sym) FB_HIP(hipMalloc(&p->amp_sym, tmp.size() * sizeof(real_t)));
+    FB_TRY(p->amp_sym.ensure(tmp.size() * sizeof(real_t)));
     FB_HIP(hipMemcpy(p->amp_sym, tmp.data(), tmp.size() * sizeof(real_t), hipMemcpyHostToDevice));
     p->amp_sym_only = 1;
     p->amp_dense = nullptr;
@@ -183,8 +183,7 @@ int FBI(potential)(fb_plan* p, const void* dk, void* out, int layout, hipStream_
 namespace {
 int finish_partials(fb_plan* p, int nblocks, double* out, hipStream_t s) {
     std::vector<double> h((size_t)nblocks);
-    FB_HIP(hipMemcpyAsync(h.data(), p->scratch, (size_t)nblocks * sizeof(double), hipMemcpyDeviceToHost, s));
-    FB_HIP(hipStreamSynchronize(s));
+    FB_TRY(fb_read_back(h.data(), p->scratch, (size_t)nblocks * sizeof(double), s));
     double t = 0.0;
     for (int q = 0; q < nblocks; ++q) t += h[(size_t)q];
     *out = t;
@@ -201,8 +200,7 @@ int reduce_blocks(long long n) {
 namespace {
 int finish_partials_max(fb_plan* p, int nblocks, double* out, hipStream_t s) {
     std::vector<double> h((size_t)nblocks);
-    FB_HIP(hipMemcpyAsync(h.data(), p->scratch, (size_t)nblocks * sizeof(double), hipMemcpyDeviceToHost, s));
-    FB_HIP(hipStreamSynchronize(s));
+    FB_TRY(fb_read_back(h.data(), p->scratch, (size_t)nblocks * sizeof(double), s));
     double t = h[0];
     for (int q = 1; q < nblocks; ++q) t = h[(size_t)q] > t ? h[(size_t)q] : t;
     *out = t;
@@ -351,8 +349,7 @@ int FBI(sep_bin)(fb_plan* p, const void* real, const double* edges_dev, double e
     long long blocks = (rows + FB_SEP_WAVES - 1) / FB_SEP_WAVES;
     if (blocks > p->prow) blocks = p->prow;
     if (blocks < 1) blocks = 1;
-    const int rb = ensure_bytes((void**)&p->sep_partials, &p->sep_partials_cap, (size_t)blocks * nv * nbins * sizeof(double));
-    if (rb) return rb;
+    FB_TRY(p->sep_partials.ensure((size_t)blocks * nv * nbins * sizeof(double)));
     if (lds > 65536) {             // more than 2 x 256 bins x 3 multipoles: up to 106 KiB of the CU's 160 KiB (nbins <= 1024)
         FB_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_sep_bin<real_t, true>),
                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -384,8 +381,7 @@ int fbi_bin_count(fb_plan* p, hipStream_t s) {
     hipLaunchKernelGGL(k_bin_count, dim3(blocks), dim3(256), lds, s, p->counts, geom(p), bin_geom(p)); }
     FB_LAUNCH_CHECK("k_bin_count");
     std::vector<unsigned long long> h(FB_MAX_BINS);
-    FB_HIP(hipMemcpyAsync(h.data(), p->counts, FB_MAX_BINS * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
-    FB_HIP(hipStreamSynchronize(s));
+    FB_TRY(fb_read_back(h.data(), p->counts, FB_MAX_BINS * sizeof(unsigned long long), s));
     for (int q = 0; q < FB_MAX_BINS; ++q) p->counts_host[q] = (double)h[(size_t)q];
     return FB_OK;
 }
@@ -471,12 +467,11 @@ int FBI(channel_means)(fb_plan* p, const void* cube, double* mean_dev, hipStream
     const int N = p->N;
     const long long npix = (long long)N * N;
     const int nb = 512 < npix ? 512 : (int)npix;
-    int r = ensure_bytes(&p->pca_work, &p->pca_work_cap, (size_t)nb * N * sizeof(double));
-    if (r) return r;
+    FB_TRY(p->work.ensure((size_t)nb * N * sizeof(double)));
     FbProfScope _ps(p, FBK_REALOP, s);
-    hipLaunchKernelGGL((k_channel_sums<real_t>), dim3(nb), dim3(256), 0, s, (const real_t*)cube, (double*)p->pca_work,
+    hipLaunchKernelGGL((k_channel_sums<real_t>), dim3(nb), dim3(256), 0, s, (const real_t*)cube, p->work.as<double>(),
                        npix, N);
-    hipLaunchKernelGGL(k_channel_means, dim3((N + 63) / 64), dim3(64, 4), 0, s, (const double*)p->pca_work, nb, N,
+    hipLaunchKernelGGL(k_channel_means, dim3((N + 63) / 64), dim3(64, 4), 0, s, p->work.as<const double>(), nb, N,
                        1.0 / (double)npix, mean_dev);
     FB_LAUNCH_CHECK("k_channel_means");
     return FB_OK;
@@ -494,21 +489,20 @@ int FBI(channel_cov)(fb_plan* p, const void* cube, const double* mean_dev, doubl
     int slices = (8 * p->num_cu + npairs - 1) / npairs;            // ~8 waves per CU (two rounds of one per SIMD)
     if (slices > npix / 64) slices = (int)(npix / 64);
     if (slices < 1) slices = 1;
-    int r = ensure_bytes(&p->pca_work, &p->pca_work_cap, (size_t)slices * N * N * sizeof(double));
-    if (r) return r;
+    FB_TRY(p->work.ensure((size_t)slices * N * N * sizeof(double)));
     { FbProfScope _ps(p, FBK_PCA, s);
     const dim3 grid(npairs, slices);
     if (MA == 4) hipLaunchKernelGGL((k_channel_cov<real_t, 4>), grid, dim3(64), 0, s, (const real_t*)cube, mean_dev,
-                                    (double*)p->pca_work, npix, N, nbs);
+                                    p->work.as<double>(), npix, N, nbs);
     else if (MA == 2) hipLaunchKernelGGL((k_channel_cov<real_t, 2>), grid, dim3(64), 0, s, (const real_t*)cube, mean_dev,
-                                         (double*)p->pca_work, npix, N, nbs);
+                                         p->work.as<double>(), npix, N, nbs);
     else if (!edge) hipLaunchKernelGGL((k_channel_cov<real_t, 1>), grid, dim3(64), 0, s, (const real_t*)cube, mean_dev,
-                                       (double*)p->pca_work, npix, N, nbs);
+                                       p->work.as<double>(), npix, N, nbs);
     else hipLaunchKernelGGL((k_channel_cov<real_t, 1, true>), grid, dim3(64), 0, s, (const real_t*)cube, mean_dev,
-                            (double*)p->pca_work, npix, N, nbs); }
+                            p->work.as<double>(), npix, N, nbs); }
     FB_LAUNCH_CHECK("k_channel_cov");
     { FbProfScope _ps(p, FBK_PCA, s);
-    hipLaunchKernelGGL(k_cov_finish, dim3((N + 63) / 64, N), dim3(64), 0, s, (const double*)p->pca_work, slices, N, bs,
+    hipLaunchKernelGGL(k_cov_finish, dim3((N + 63) / 64, N), dim3(64), 0, s, p->work.as<const double>(), slices, N, bs,
                        1.0 / (double)(npix - 1), cov_dev); }
     FB_LAUNCH_CHECK("k_cov_finish");
     return FB_OK;

@@ -228,11 +228,6 @@ FofWork work_layout(unsigned long long n, unsigned long long ncells) {
     w.total = o;
     return w;
 }
-int read_small(const void* work, FofSmall* h, hipStream_t s) {
-    FB_HIP(hipMemcpyAsync(h, work, sizeof(FofSmall), hipMemcpyDeviceToHost, s));
-    FB_HIP(hipStreamSynchronize(s));
-    return FB_OK;
-}
 int loop_error() {
     fb_set_error("friends-of-friends: a find or union loop hit its iteration cap");
     return FB_ERR_STATE;
@@ -284,11 +279,9 @@ int fb_fof_link(fb_plan* p, const double* pos, int64_t n, double link, const int
     hipLaunchKernelGGL(k_fof_bin, dim3(grid_for(un, p)), dim3(256), 0, s, pos, un, g, cellid, cursor, &sm->err);
     FB_LAUNCH_CHECK("k_fof_bin");
     FofSmall h;
-    int r = read_small(sm, &h, s);
-    if (r) return r;
+    FB_TRY(fb_read_back(&h, sm, sizeof(h), s));
     if (h.err & FB_FOF_ERR_POS) { *bad = 1; return FB_OK; }          // before any linking
-    r = exscan(ScanPlain{cursor}, ncells, csum, start, s);           // start[ncells] = n
-    if (r) return r;
+    FB_TRY(exscan(ScanPlain{cursor}, ncells, csum, start, s));       // start[ncells] = n
     FB_HIP(hipMemsetAsync(cursor, 0, (size_t)ncells * 4, s));
     hipLaunchKernelGGL(k_fof_scatter, dim3(grid_for(un, p)), dim3(256), 0, s, pos, un, g, (const unsigned*)cellid, (const unsigned*)start,
                        cursor, perm, spos, (unsigned*)root_out);
@@ -296,8 +289,7 @@ int fb_fof_link(fb_plan* p, const double* pos, int64_t n, double link, const int
     hipLaunchKernelGGL(k_fof_items, dim3(grid_for(ncells, p)), dim3(256), 0, s, (const unsigned*)start, ncells, items, &sm->count);
     FB_LAUNCH_CHECK("k_fof_items");
     if (stage_ms) FB_HIP(hipEventRecord(ev[1], s));
-    r = read_small(sm, &h, s);
-    if (r) return r;
+    FB_TRY(fb_read_back(&h, sm, sizeof(h), s));
     const unsigned long long nitems = h.count;
     // 2. link: tile 0 of every cell, then the further tiles of the crowded cells
     const int half = ncell[0] >= 3 && ncell[1] >= 3 && ncell[2] >= 3;
@@ -323,8 +315,7 @@ int fb_fof_link(fb_plan* p, const double* pos, int64_t n, double link, const int
         FB_HIP(hipMemsetAsync(&sm->changed, 0, sizeof(unsigned), s));
         hipLaunchKernelGGL(k_fof_jump, dim3(grid_for(un, p)), dim3(256), 0, s, (unsigned*)root_out, un, &sm->changed);
         FB_LAUNCH_CHECK("k_fof_jump");
-        r = read_small(sm, &h, s);
-        if (r) return r;
+        FB_TRY(fb_read_back(&h, sm, sizeof(h), s));
         if (h.err & FB_FOF_ERR_LOOP) return loop_error();
         if (!h.changed) break;
     }
@@ -359,8 +350,7 @@ int fb_fof_sizes(fb_plan* p, const uint32_t* root, int64_t n, int64_t nmin, void
                        (unsigned)std::min<int64_t>(nmin, 0xFFFFFFFFll), (unsigned*)kept_out, &sm->count, &sm->groups);
     FB_LAUNCH_CHECK("k_fof_tally");
     FofSmall h;
-    const int r = read_small(sm, &h, s);
-    if (r) return r;
+    FB_TRY(fb_read_back(&h, sm, sizeof(h), s));
     out_host[0] = (int64_t)h.groups;
     out_host[1] = (int64_t)h.count;
     return FB_OK;
@@ -393,8 +383,7 @@ int fb_fof_catalogue(fb_plan* p, const double* pos, const double* vel, const uin
         hipLaunchKernelGGL(k_fof_vmax, dim3(grid_for(3 * un, p)), dim3(256), 0, s, vel, 3 * un, &sm->vmax_bits, &sm->err);
         FB_LAUNCH_CHECK("k_fof_vmax");
         FofSmall h;
-        const int r = read_small(sm, &h, s);
-        if (r) return r;
+        FB_TRY(fb_read_back(&h, sm, sizeof(h), s));
         double vmax;
         memcpy(&vmax, &h.vmax_bits, sizeof(vmax));
         if ((h.err & FB_FOF_ERR_VEL) || !std::isfinite((double)n * vmax)) { *bad = 4; return FB_OK; }     // the sums' bound

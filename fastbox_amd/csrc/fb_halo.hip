@@ -329,10 +329,6 @@ __global__ __launch_bounds__(256) void k_paint_compensate(T* half, int N, int NR
     }
 }
 
-int ensure_small(fb_plan* p) {
-    if (!p->halo_small) FB_HIP(hipMalloc(&p->halo_small, FB_HALO_SMALL));
-    return FB_OK;
-}
 fb::RngKey rng_key(uint64_t seed, uint64_t real) {
     fb::RngKey k;
     k.k[0] = (uint32_t)seed; k.k[1] = (uint32_t)(seed >> 32); k.k[2] = (uint32_t)real; k.k[3] = (uint32_t)(real >> 32);
@@ -350,9 +346,9 @@ template <typename T, bool COUNTS>
 int halo_lambda(fb_plan* p, const void* delta, HPrm nbar, HPrm bias, double vv, int lognormal, double* lam_out, void* counts_out,
                 uint64_t seed, uint64_t real, hipStream_t s) {
     const unsigned long long n = (unsigned long long)p->N * p->N * p->N;
-    int r = ensure_small(p);
+    int r = p->halo_small.ensure(FB_HALO_SMALL);
     if (r) return r;
-    double* part = (double*)p->halo_small;               // [FB_HALO_RED_BLOCKS] partials
+    double* part = p->halo_small.as<double>();           // [FB_HALO_RED_BLOCKS] partials
     double* stats = part + FB_HALO_RED_BLOCKS;           // [shift, sum]
     unsigned* flag = (unsigned*)(stats + 2);
     FB_HIP(hipMemsetAsync(flag, 0, sizeof(unsigned), s));
@@ -381,9 +377,9 @@ int halo_lambda(fb_plan* p, const void* delta, HPrm nbar, HPrm bias, double vv, 
 template <typename T>
 int cat_stats(fb_plan* p, const void* counts, int64_t* out_host, hipStream_t s) {
     const unsigned long long n = (unsigned long long)p->N * p->N * p->N;
-    int r = ensure_small(p);
+    int r = p->halo_small.ensure(FB_HALO_SMALL);
     if (r) return r;
-    unsigned long long* part = (unsigned long long*)p->halo_small;
+    unsigned long long* part = p->halo_small.as<unsigned long long>();
     const int nb = std::min(grid_for(n, p), FB_HALO_RED_BLOCKS - 2);
     unsigned long long* res = part + 3 * (FB_HALO_RED_BLOCKS - 2);
     hipLaunchKernelGGL((k_cat_stats<T>), dim3(nb), dim3(256), 0, s, (const T*)counts, n, part);
@@ -391,8 +387,7 @@ int cat_stats(fb_plan* p, const void* counts, int64_t* out_host, hipStream_t s) 
     hipLaunchKernelGGL(k_cat_stats_finish, dim3(1), dim3(256), 0, s, (const unsigned long long*)part, nb, res);
     FB_LAUNCH_CHECK("k_cat_stats_finish");
     unsigned long long h[3];
-    FB_HIP(hipMemcpyAsync(h, res, sizeof(h), hipMemcpyDeviceToHost, s));
-    FB_HIP(hipStreamSynchronize(s));
+    FB_TRY(fb_read_back(h, res, sizeof(h), s));
     FB_REQUIRE(!h[2], "halo counts must be non-negative integers");
     out_host[0] = (int64_t)h[0];
     out_host[1] = (int64_t)h[1];
@@ -411,11 +406,11 @@ int cat_emit(fb_plan* p, const void* counts, int64_t kmax, const double* U, int 
     const unsigned long long M = K * nb;
     // work: H [M] u32 | S [M + 1] u64 (S[M]: the total, not read) | csum [chunks] u64
     const size_t offS = (M * 4 + 15) / 16 * 16, offC = offS + (M + 1) * 8;
-    int r = ensure_bytes(&p->halo_work, &p->halo_work_cap, offC + (size_t)scan_chunks(M) * 8);
+    int r = p->halo_work.ensure(offC + (size_t)scan_chunks(M) * 8);
     if (r) return r;
-    unsigned* H = (unsigned*)p->halo_work;
-    unsigned long long* S = (unsigned long long*)((char*)p->halo_work + offS);
-    unsigned long long* csum = (unsigned long long*)((char*)p->halo_work + offC);
+    unsigned* H = p->halo_work.as<unsigned>();
+    unsigned long long* S = (unsigned long long*)(p->halo_work.as<char>() + offS);
+    unsigned long long* csum = (unsigned long long*)(p->halo_work.as<char>() + offC);
     FB_HIP(hipMemsetAsync(H, 0, M * 4, s));
     { FbProfScope _ps(p, FBK_REALOP, s);
     hipLaunchKernelGGL((k_cat_hist<T>), dim3(nb), dim3(256), 0, s, (const T*)counts, n, tile, nb, (int)kmax, H); }
@@ -433,12 +428,12 @@ template <typename T>
 int paint(fb_plan* p, const double* pos, const double* wt, unsigned long long n, int window, void* out, hipStream_t s) {
     const unsigned long long nv = (unsigned long long)p->N * p->N * p->N;
     constexpr bool TWO = sizeof(T) == 8;
-    int r = ensure_small(p);
-    if (!r) r = ensure_bytes(&p->halo_acc, &p->halo_acc_cap, nv * 8 * (TWO ? 2 : 1));
+    int r = p->halo_small.ensure(FB_HALO_SMALL);
+    if (!r) r = p->halo_acc.ensure(nv * 8 * (TWO ? 2 : 1));
     if (r) return r;
-    double* part = (double*)p->halo_small;
+    double* part = p->halo_small.as<double>();
     double* wsum = part + FB_HALO_RED_BLOCKS;
-    unsigned long long* hi = (unsigned long long*)p->halo_acc;
+    unsigned long long* hi = p->halo_acc.as<unsigned long long>();
     unsigned long long* lo = TWO ? hi + nv : nullptr;
     FB_HIP(hipMemsetAsync(hi, 0, nv * 8 * (TWO ? 2 : 1), s));
     const int nb = std::min(grid_for(n, p), FB_HALO_RED_BLOCKS);
@@ -498,9 +493,8 @@ int fb_halo_counts(fb_plan* p, const void* delta, const void* nbar, int nbar_kin
                     (halo_lambda<double, true>(p, delta, nb, bs, voxel_vol, lognormal, nullptr, counts_out, seed, realisation, s)));
     if (r) return r;
     unsigned flag = 0;
-    const unsigned* fdev = (const unsigned*)((double*)p->halo_small + FB_HALO_RED_BLOCKS + 2);
-    FB_HIP(hipMemcpyAsync(&flag, fdev, sizeof(flag), hipMemcpyDeviceToHost, s));
-    FB_HIP(hipStreamSynchronize(s));
+    const unsigned* fdev = (const unsigned*)(p->halo_small.as<double>() + FB_HALO_RED_BLOCKS + 2);
+    FB_TRY(fb_read_back(&flag, fdev, sizeof(flag), s));
     *too_large = flag ? 1 : 0;
     return FB_OK;
 }

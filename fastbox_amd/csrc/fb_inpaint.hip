@@ -417,9 +417,8 @@ int replace_nan(fb_plan* p, const void* cube, void* out, double* mean_out, hipSt
     if (slices > 256) slices = 256;
     const int nrows = 4 * slices;
     // work: [mean: N | sums: nrows N | counts: nrows N]
-    int r = ensure_bytes(&p->pca_work, &p->pca_work_cap, (size_t)(1 + 2 * nrows) * N * sizeof(double));
-    if (r) return r;
-    double* mean = (double*)p->pca_work;
+    FB_TRY(p->work.ensure((size_t)(1 + 2 * nrows) * N * sizeof(double)));
+    double* mean = p->work.as<double>();
     double* psum = mean + N;
     double* pcnt = psum + (size_t)nrows * N;
     FbProfScope _ps(p, FBK_PCA, s);
@@ -476,10 +475,10 @@ int fb_gcr_solve(fb_plan* p, const double* sqrtS_dev, const double* P_dev, const
     double* t = work + 3 * n;
     double* z = P_dev ? work + 4 * n : r;                 // without a preconditioner z is r itself
     // row state: [rz | bb | res: npix doubles each | summary: 4 | active: npix ints | count: 2 ints]
-    int rc = ensure_bytes(&p->pca_work, &p->pca_work_cap, (size_t)npix * (3 * sizeof(double) + sizeof(int)) + 4 * sizeof(double) + 2 * sizeof(int));
+    int rc = p->work.ensure((size_t)npix * (3 * sizeof(double) + sizeof(int)) + 4 * sizeof(double) + 2 * sizeof(int));
     if (rc) return rc;
     GcrRows st;
-    st.rz = (double*)p->pca_work;
+    st.rz = p->work.as<double>();
     st.bb = st.rz + npix;
     double* res = st.bb + npix;
     double* summary = res + npix;
@@ -491,8 +490,7 @@ int fb_gcr_solve(fb_plan* p, const double* sqrtS_dev, const double* P_dev, const
     FB_HIP(hipMemsetAsync(st.count, 0, sizeof(int), s));
     hipLaunchKernelGGL(k_cg_init, rows, dim3(256), 0, s, b, x, r, st, npix, N);
     FB_LAUNCH_CHECK("k_cg_init");
-    FB_HIP(hipMemcpyAsync(&active, st.count, sizeof(int), hipMemcpyDeviceToHost, s));
-    FB_HIP(hipStreamSynchronize(s));
+    FB_TRY(fb_read_back(&active, st.count, sizeof(int), s));
     int it = 0;
     for (; active > 0 && it < maxiter; ++it) {
         if (P_dev) { rc = los_matmul<double>(p, P_dev, r, nullptr, nullptr, nullptr, z, s); if (rc) return rc; }
@@ -502,8 +500,7 @@ int fb_gcr_solve(fb_plan* p, const double* sqrtS_dev, const double* P_dev, const
         FB_HIP(hipMemsetAsync(st.count, 0, sizeof(int), s));
         hipLaunchKernelGGL(k_cg_step, rows, dim3(256), 0, s, (const double*)pd, (const double*)ap, x, r, st, tol * tol, npix, N);
         FB_LAUNCH_CHECK("k_cg_step");
-        FB_HIP(hipMemcpyAsync(&active, st.count, sizeof(int), hipMemcpyDeviceToHost, s));
-        FB_HIP(hipStreamSynchronize(s));
+        FB_TRY(fb_read_back(&active, st.count, sizeof(int), s));
     }
     // the true residual, from one more application of A
     rc = apply_A(p, sqrtS_dev, q, x, t, ap, s);
@@ -512,8 +509,7 @@ int fb_gcr_solve(fb_plan* p, const double* sqrtS_dev, const double* P_dev, const
     hipLaunchKernelGGL(k_gcr_summary, dim3(1), dim3(1024), 0, s, (const double*)res, (const int32_t*)n_iter_dev, (const int*)st.active, npix, summary);
     FB_LAUNCH_CHECK("k_gcr_summary");
     double h[3];
-    FB_HIP(hipMemcpyAsync(h, summary, sizeof(h), hipMemcpyDeviceToHost, s));
-    FB_HIP(hipStreamSynchronize(s));
+    FB_TRY(fb_read_back(h, summary, sizeof(h), s));
     info_out[0] = h[0]; info_out[1] = h[1]; info_out[2] = h[2]; info_out[3] = (double)it;
     return FB_OK;
 }

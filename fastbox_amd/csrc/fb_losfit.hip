@@ -460,19 +460,11 @@ int subtract(fb_plan* p, const void* X, const double* Y, const double* shift, vo
     return FB_OK;
 }
 
-// the counter of failed rows lives at the start of the plan's cleaning work buffer
+// the counter of failed rows lives at the start of the plan's shared work buffer; the entry points read it back before they return
 int failed_begin(fb_plan* p, int** counter, hipStream_t s) {
-    const int r = ensure_bytes(&p->pca_work, &p->pca_work_cap, sizeof(int));
-    if (r) return r;
-    *counter = (int*)p->pca_work;
+    FB_TRY(p->work.ensure(sizeof(int)));
+    *counter = p->work.as<int>();
     FB_HIP(hipMemsetAsync(*counter, 0, sizeof(int), s));
-    return FB_OK;
-}
-int failed_end(const int* counter, int32_t* n_failed_out, hipStream_t s) {
-    int h = 0;
-    FB_HIP(hipMemcpyAsync(&h, counter, sizeof(int), hipMemcpyDeviceToHost, s));
-    FB_HIP(hipStreamSynchronize(s));
-    *n_failed_out = h;
     return FB_OK;
 }
 bool kind_ok(const void* a, int kind) { return !a || kind == FB_GCR_PER_CHANNEL || kind == FB_GCR_PER_VOXEL; }
@@ -499,7 +491,7 @@ int fb_los_polyfit(fb_plan* p, const void* cube, const void* w, int w_kind, cons
     if (r) return r;
     r = FB_DISPATCH(p, polyfit<float>(p, a, s), polyfit<double>(p, a, s));
     if (r) return r;
-    return failed_end(a.n_failed, n_failed_out, s);
+    return fb_read_back(n_failed_out, a.n_failed, sizeof(int32_t), s);
 }
 
 int fb_los_powerlaw(fb_plan* p, const void* maps, const double* tpsmean_dev, const void* sigma, int sigma_kind, const void* w,
@@ -520,7 +512,7 @@ int fb_los_powerlaw(fb_plan* p, const void* maps, const double* tpsmean_dev, con
     if (r) return r;
     r = FB_DISPATCH(p, powerlaw<float>(p, a, s), powerlaw<double>(p, a, s));
     if (r) return r;
-    return failed_end(a.n_failed, n_failed_out, s);
+    return fb_read_back(n_failed_out, a.n_failed, sizeof(int32_t), s);
 }
 
 int fb_los_subtract(fb_plan* p, const void* X, const double* Y, const double* shift_dev, void* cube_out, void* stream) {

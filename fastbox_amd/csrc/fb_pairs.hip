@@ -265,8 +265,7 @@ int fb_pair_count(fb_plan* p, const double* pos1, int64_t n1, const double* pos2
         FB_LAUNCH_CHECK("k_fof_bin");
     }
     PairSmall h;
-    FB_HIP(hipMemcpyAsync(&h, sm, sizeof(h), hipMemcpyDeviceToHost, s));
-    FB_HIP(hipStreamSynchronize(s));                                  // (the edges have been read by now, too)
+    FB_TRY(fb_read_back(&h, sm, sizeof(h), s));   // (the edges have been read by now, too)
     if (h.err & FB_FOF_ERR_POS) { *bad = 1; return FB_OK; }
     if (n1 == 0 || (!autoc && n2 == 0)) return FB_OK;                 // no pair: the counts are zero
     for (int q = 0; q < ncat; ++q) {
@@ -287,8 +286,7 @@ int fb_pair_count(fb_plan* p, const double* pos1, int64_t n1, const double* pos2
     hipLaunchKernelGGL(k_fof_items, dim3(grid_for(ncells, p)), dim3(256), 0, s, hstart, ncells, items, &sm->items);
     FB_LAUNCH_CHECK("k_fof_items");
     if (stage_ms) FB_HIP(hipEventRecord(ev[1], s));
-    FB_HIP(hipMemcpyAsync(&h, sm, sizeof(h), hipMemcpyDeviceToHost, s));
-    FB_HIP(hipStreamSynchronize(s));
+    FB_TRY(fb_read_back(&h, sm, sizeof(h), s));
     const unsigned long long nitems = h.items;
     // 2. the sweep: tile 0 of every cell, then the further tiles of the crowded cells
     PairBins pb;

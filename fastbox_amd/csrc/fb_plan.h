@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "fb_keyed_cache.h"
 #include <string>
 #include <vector>
 
@@ -13,8 +14,55 @@
 #define FB_ERR_STATE -5
 #define FB_ERR_RCCL -6
 
+void fb_set_error(const std::string& msg);
+int fb_hip_check(hipError_t e, const char* what);
+#define FB_HIP(x) do { int _r = fb_hip_check((x), #x); if (_r) return _r; } while (0)
+#define FB_TRY(x) do { const int _r = (x); if (_r) return _r; } while (0)        // x: a call that returns an FB_* status
+#define FB_LAUNCH_CHECK(name) do { int _r = fb_hip_check(hipGetLastError(), name); if (_r) return _r; } while (0)
+
+// Device memory owned by the plan (or by an entry of one of its caches): freed by the destructor, so whoever destroys it makes
+// the plan's device current first (fb_plan_destroy; every entry point does).  Grow-only: ensure(bytes) keeps storage that is
+// large enough and otherwise frees it before allocating anew -- the contents are lost, and a failed allocation (FB_ERR_NOMEM)
+// leaves the buffer empty.  T is what the buffer converts to; as<U>() reads it as another type (the tables in plan precision).
+template <typename T = void> struct FbBuf {
+    T* ptr = nullptr;
+    size_t cap = 0;              // bytes
+    FbBuf() = default;
+    FbBuf(FbBuf&& o) noexcept : ptr(o.ptr), cap(o.cap) { o.ptr = nullptr; o.cap = 0; }
+    FbBuf(const FbBuf&) = delete;
+    FbBuf& operator=(const FbBuf&) = delete;
+    ~FbBuf() { if (ptr) (void)hipFree(ptr); }
+    operator T*() const { return ptr; }
+    template <typename U> U* as() const { return static_cast<U*>(static_cast<void*>(ptr)); }
+    int ensure(size_t need) { return cap >= need ? FB_OK : grow(need); }
+    int reset() {                // back to empty
+        T* q = ptr;
+        ptr = nullptr; cap = 0;
+        if (q) FB_HIP(hipFree(q));
+        return FB_OK;
+    }
+private:
+    __attribute__((noinline)) int grow(size_t need) {       // the rare path stays out of line, so that ensure() inlines to its comparison
+        FB_TRY(reset());
+        FB_HIP(hipMalloc(reinterpret_cast<void**>(&ptr), need));
+        cap = need;
+        return FB_OK;
+    }
+};
+
 struct fb_comm;                  // fb_comm.inc: RCCL communicator + its stream and events (fb_comm_create)
-struct fb_cyl_rows;              // fb_cyl.hip: one k_perp edge set's sorted transverse rows
+
+// One k_perp edge set's transverse rows (m_x, m_y), as i N + j, sorted by bin (ascending inside a bin): what both estimators
+// of fb_cyl.hip gather through.  A row lies in bin np.digitize(k_perp, edges) - 1 with k_perp = sqrt(k_x k_x + k_y k_y) formed
+// on the host exactly as numpy forms it; rows outside [edges[0], edges[nb]) are not listed.  The plan's cache keys an entry by
+// (edges[nb + 1], skip0); skip0: the row m_perp = 0 is left out.
+struct fb_cyl_rows {
+    int nb = 0;
+    FbBuf<int> rows_dev;                 // [off[nb]]
+    std::vector<int> off;                // [nb + 1] first row of each bin
+    std::vector<double> sumk;            // [nb] sum of k_perp over the bin's rows
+    bool has0 = false;                   // the row m_perp = 0 is listed (in bin 0: k_perp = 0)
+};
 
 struct fb_plan {
     fb_comm* comm = nullptr;     // one box over several GPUs: this rank's communicator, or null
@@ -37,81 +85,75 @@ struct fb_plan {
     int NR = 0;              // stored rows per x-plane of a half spectrum (N + 1: see KGeom::NR)
     int cubic = 0;           // Lx == Ly == Lz (integer shells usable)
 
-    void* tw = nullptr;      // forward twiddles W_N^j, j < N, in plan precision
-    double* axis2 = nullptr; // [3][N] (m_i / L_a)^2 exactly as numpy computes it (box.py:125-127)
-    double* kpar = nullptr;  // [N]  2 pi m / Lz
-    double* ksc = nullptr;   // [3][N] m_i * (2 pi / L_a)  (velocity numerators, box.py:254-256)
-    double* zgrid = nullptr; // [N]  self.z
+    FbBuf<> tw;              // forward twiddles W_N^j, j < N, in plan precision
+    FbBuf<double> axis2;     // [3][N] (m_i / L_a)^2 exactly as numpy computes it (box.py:125-127)
+    FbBuf<double> kpar;      // [N]  2 pi m / Lz
+    FbBuf<double> ksc;       // [3][N] m_i * (2 pi / L_a)  (velocity numerators, box.py:254-256)
+    FbBuf<double> zgrid;     // [N]  self.z
 
     // sqrt(P(k) boxfactor) lookup (box.py:161-176)
-    void* amp_shell = nullptr;   // [nshell] plan precision, index n^2 = i^2+j^2+l^2 (cubic only)
+    FbBuf<> amp_shell;           // [nshell] plan precision, index n^2 = i^2+j^2+l^2 (cubic only)
     int64_t nshell = 0;
     const void* amp_dense = nullptr;  // caller-owned [N][N][NZP]
-    void* pca_work = nullptr;    // channel-sum / covariance partials (grown on demand)
-    size_t pca_work_cap = 0;
-    double* kperp_tab = nullptr; // [N][N] 2 pi sqrt((m_x/L_x)^2 + (m_y/L_y)^2), box.py:374
+    // The shared work buffer of the cleaning, in-painting, bispectrum, line-of-sight-fit and channel mean / covariance entry
+    // points.  The rule that lets them share it: its contents are undefined on entry to every entry point, and no entry point
+    // keeps a pointer into it after it returns -- each lays it out anew (its ensure() may move it).  Whatever has to outlive a
+    // call gets a buffer of its own.
+    FbBuf<> work;
+    FbBuf<double> eig_work;      // [4 n^2 + 2] of fb_leading_eigenvectors: its input may be a covariance computed through `work`
+    FbBuf<double> kperp_tab;     // [N][N] 2 pi sqrt((m_x/L_x)^2 + (m_y/L_y)^2), box.py:374
     int amp_sym_only = 0;        // amp_sym was given directly (any box shape); no shell table behind it
-    void* amp_sym = nullptr;     // [N/2+1][N/2+1][NZP] plan precision: amp_shell spread over (|m_x|, |m_y|, k_z)
+    FbBuf<> amp_sym;             // [N/2+1][N/2+1][NZP] plan precision: amp_shell spread over (|m_x|, |m_y|, k_z)
 
     // P(k) binning (box.py:745-764)
-    double* bins = nullptr;      // [nbins] edges
+    FbBuf<double> bins;          // [nbins] edges
     int nbins = 0;
-    int* thr = nullptr;          // [FB_MAX_BINS] shell thresholds (cubic boxes)
+    FbBuf<int> thr;              // [FB_MAX_BINS] shell thresholds (cubic boxes)
     int use_thr = 0;             // 0: decide every mode with the exact fp64 |k|
     int namb = 0;
     int amb[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    unsigned long long* counts = nullptr;  // [FB_MAX_BINS] device
+    FbBuf<unsigned long long> counts;      // [FB_MAX_BINS] device
     double counts_host[256];
-    double* partials = nullptr;  // [prow][3*FB_MAX_BINS] per-workgroup partial sums
+    FbBuf<double> partials;      // [prow][3*FB_MAX_BINS] per-workgroup partial sums
     int prow = 0;
-    double* scratch = nullptr;   // small reduction scratch [FB_SCRATCH]
-    double* bin_partials = nullptr;   // fused binning: [workgroups][2*nbins]
-    size_t bin_partials_cap = 0;      // bytes, like every *_cap below: the buffers grow through ensure_bytes
+    FbBuf<double> scratch;       // small reduction scratch [FB_SCRATCH]
+    FbBuf<double> bin_partials;       // fused binning: [workgroups][2*nbins] (grown on demand)
     long long bin_rows = 0;
     long long bin_rows_main = 0;      // of which the fused binning pass itself wrote (the rest: k_bin_packed_plane)
-    long long bin_append_cap = 0;     // > 0: binning launches append their columns to a shared table of this many (k_z chunks)
-    void* plane_buf = nullptr;        // packed work spectra: the shared plane column after the last forward pass, [N][N] complex
-    double* exp_partials = nullptr;   // r2c with exp(): [workgroups]
-    size_t exp_partials_cap = 0;
+    long long bin_append_cols = 0;    // > 0: binning launches append their columns to a shared table of this many (k_z chunks)
+    FbBuf<> plane_buf;                // packed work spectra: the shared plane column after the last forward pass, [N][N] complex
+    FbBuf<double> exp_partials;       // r2c with exp(): [workgroups] (grown on demand)
     long long exp_rows = 0;
     long long exp_base = 0;           // block offset of the plane batch being launched (fb_fft_launch.inc yz_passes)
 
     // correlation function (fb_bin_separation): edges on the device, and the data-independent sums (cells, sum |s|) per
-    // bin set already computed -- [edges..., cells..., sum |s|...] per entry, most recent last
-    double* sep_edges = nullptr;      // [FB_MAX_SEP_BINS + 1]
-    std::vector<std::vector<double>> sep_geom;
-    double* sep_partials = nullptr;   // [nv nbins][workgroups] of k_sep_bin (grown on demand: up to 3 x 1024 values per workgroup)
-    size_t sep_partials_cap = 0;
+    // bin set already computed -- key [edges...], value [cells..., sum |s|...]
+    FbBuf<double> sep_edges;          // [FB_MAX_SEP_BINS + 1] (allocated on first use)
+    FbKeyedCache<std::vector<double>, 16> sep_geom;
+    FbBuf<double> sep_partials;       // [nv nbins][workgroups] of k_sep_bin (grown on demand: up to 3 x 1024 values per workgroup)
 
     // power spectrum in (k, mu) bins (fb_power.hip): the bin table on the device, per-workgroup partials, and the
-    // data-independent sums (modes, sum |k|, sum mu per cell) per (edges, nmu) already computed -- [edges..., nmu, modes...,
-    // sum |k|..., sum mu...] per entry, most recent last
-    double* pk_tab = nullptr;         // [FB_PK_MAX_K + FB_PK_MAX_MU + 2]
-    double* pk_partials = nullptr;    // [values][workgroups] of k_pk_bin (grown on demand)
-    size_t pk_partials_cap = 0;
-    std::vector<std::vector<double>> pk_geom;
+    // data-independent sums (modes, sum |k|, sum mu per cell) per (edges, nmu) already computed -- key [edges..., nmu], value
+    // [modes..., sum |k|..., sum mu...]
+    FbBuf<double> pk_tab;             // [FB_PK_MAX_K + FB_PK_MAX_MU + 2] (allocated on first use)
+    FbBuf<double> pk_partials;        // [values][workgroups] of k_pk_bin (grown on demand)
+    FbKeyedCache<std::vector<double>, 16> pk_geom;
 
     // cylindrical power and multi-frequency angular power (fb_cyl.hip): the transverse rows sorted by k_perp bin per edge set
-    // already seen (most recent last; freed by fb_cyl_release), the chunk / fold tables of the call in flight, the partials
-    std::vector<fb_cyl_rows*> cyl_rows;
-    int* cyl_idx = nullptr;           // [3 chunks][nb + 1 chunk offsets][2 npar m_z ranges] (grown on demand)
-    size_t cyl_idx_cap = 0;
-    double* cyl_tab = nullptr;        // [nb] Lx Ly / (N^4 modes_b) of fb_transverse_gram (grown on demand)
-    size_t cyl_tab_cap = 0;
-    double* cyl_partials = nullptr;   // [chunks][N/2 + 1] of k_cyl_rows (grown on demand)
-    size_t cyl_partials_cap = 0;
+    // already seen, the chunk / fold tables of the call in flight, the partials
+    FbKeyedCache<fb_cyl_rows, 8> cyl_rows;
+    FbBuf<int> cyl_idx;               // [3 chunks][nb + 1 chunk offsets][2 npar m_z ranges] (grown on demand)
+    FbBuf<double> cyl_tab;            // [nb] Lx Ly / (N^4 modes_b) of fb_transverse_gram (grown on demand)
+    FbBuf<double> cyl_partials;       // [chunks][N/2 + 1] of k_cyl_rows (grown on demand)
 
     // halo tracers (fb_halo.hip): reduction partials, the catalogue's (count, block) tables, the painting accumulators
-    void* halo_small = nullptr;       // [FB_HALO_SMALL] bytes
-    void* halo_work = nullptr;        // grown on demand
-    size_t halo_work_cap = 0;         // bytes
-    void* halo_acc = nullptr;         // grown on demand
-    size_t halo_acc_cap = 0;          // bytes
+    FbBuf<> halo_small;               // [FB_HALO_SMALL] bytes (allocated on first use)
+    FbBuf<> halo_work;                // grown on demand
+    FbBuf<> halo_acc;                 // grown on demand
 
     // void finding (fb_voids.hip): flags and reduction partials, and the per-label / per-tile work tables
-    void* void_small = nullptr;       // [FB_VOID_SMALL] bytes
-    void* void_work = nullptr;        // grown on demand
-    size_t void_work_cap = 0;         // bytes
+    FbBuf<> void_small;               // [FB_VOID_SMALL] bytes (allocated on first use)
+    FbBuf<> void_work;                // grown on demand
 
     // second stream for alternate plane batches of the y/z passes (created on first use)
     hipStream_t aux_stream = nullptr;
@@ -155,21 +197,6 @@ struct FbProfScope {
 #define FB_PK_MAX_MU 128         // mu bins
 #define FB_PK_MAX_VALUES 5120    // nk nmu (lmax / 2 + 1): one wave's LDS row of 40 KiB (1024 k bins x 5 mu bins)
 #define FB_SCRATCH 8192
-
-void fb_set_error(const std::string& msg);
-int fb_hip_check(hipError_t e, const char* what);
-#define FB_HIP(x) do { int _r = fb_hip_check((x), #x); if (_r) return _r; } while (0)
-#define FB_LAUNCH_CHECK(name) do { int _r = fb_hip_check(hipGetLastError(), name); if (_r) return _r; } while (0)
-// grow-only device work buffer (the plan's pca_work and its like): the one policy for every buffer of the plan that grows on
-// demand; *cap is in bytes
-static inline int ensure_bytes(void** buf, size_t* cap, size_t need) {
-    if (*cap >= need) return FB_OK;
-    if (*buf) FB_HIP(hipFree(*buf));
-    *buf = nullptr; *cap = 0;
-    FB_HIP(hipMalloc(buf, need));
-    *cap = need;
-    return FB_OK;
-}
 
 // ---- per-precision launchers (fb_fft_launch.inc, fb_field_launch.inc) ------------
 #define FB_DECL(sfx) \
@@ -264,5 +291,4 @@ static inline int ensure_bytes(void** buf, size_t* cap, size_t need) {
 FB_DECL(f32)
 FB_DECL(f64)
 int fbi_bin_count(fb_plan* p, hipStream_t s);
-void fb_cyl_release(fb_plan* p);     // fb_cyl.hip: frees the plan's sorted-row lists (fb_plan_destroy)
 int fbi_slab_permute(fb_plan* p, const void* in, void* out, int nxl, int nparts, int pack, hipStream_t s);

@@ -193,8 +193,7 @@ int pk_launch(fb_plan* p, bool geom, int which, const void* h1, const void* h2, 
     const long long resident = std::max(1LL, std::min(8LL, (long long)((160 * 1024) / lds)));   // workgroups per CU
     long long blocks = std::min((rows + waves - 1) / waves, resident * p->num_cu);
     if (blocks < 1) blocks = 1;
-    const int rb = ensure_bytes((void**)&p->pk_partials, &p->pk_partials_cap, (size_t)blocks * a.nv * nc * sizeof(double));
-    if (rb) return rb;
+    FB_TRY(p->pk_partials.ensure((size_t)blocks * a.nv * nc * sizeof(double)));
     const void* fn = geom ? PkKernels<T>::geom() : PkKernels<T>::data();
     if (lds > 65536) FB_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     { FbProfScope _ps(p, FBK_BIN, s);
@@ -228,7 +227,7 @@ int bin_power_kmu(fb_plan* p, const void* half1, const void* half2, const double
     const double step = 1.0 / nmu;
     for (int q = 0; q <= nmu; ++q) tab[nk + 1 + q] = (double)q * step + 0.0;
     tab[nk + 1 + nmu] = 1.0;
-    if (!p->pk_tab) FB_HIP(hipMalloc((void**)&p->pk_tab, (FB_PK_MAX_K + FB_PK_MAX_MU + 2) * sizeof(double)));
+    FB_TRY(p->pk_tab.ensure((FB_PK_MAX_K + FB_PK_MAX_MU + 2) * sizeof(double)));
     FB_HIP(hipMemcpyAsync(p->pk_tab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, s));
     PkArgs a;
     a.tab = p->pk_tab; a.N = p->N; a.NZV = p->NZV; a.NZP = p->NZP; a.NR = p->NR;
@@ -243,33 +242,25 @@ int bin_power_kmu(fb_plan* p, const void* half1, const void* half2, const double
     // the data-independent sums: once per (edges, nmu)
     std::vector<double> key(kedges, kedges + nk + 1);
     key.push_back((double)nmu);
-    const std::vector<double>* geo = nullptr;
-    for (const auto& e : p->pk_geom)
-        if (e.size() == key.size() + 3 * (size_t)nc && std::equal(key.begin(), key.end(), e.begin())) geo = &e;
+    const std::vector<double>* geo = p->pk_geom.find(key);
     if (!geo) {
-        std::vector<double> e(key);
-        e.resize(key.size() + 3 * (size_t)nc);
+        std::vector<double> e(3 * (size_t)nc);
         PkArgs g = a;
         g.nv = 1;
         for (int w = 0; w < 3; ++w) {
             int r = FB_DISPATCH(p, pk_launch<float>(p, true, w, nullptr, nullptr, g, p->scratch, s),
                                 pk_launch<double>(p, true, w, nullptr, nullptr, g, p->scratch, s));
             if (r) return r;
-            FB_HIP(hipMemcpyAsync(e.data() + key.size() + (size_t)w * nc, p->scratch, (size_t)nc * sizeof(double),
-                                  hipMemcpyDeviceToHost, s));
-            FB_HIP(hipStreamSynchronize(s));
+            FB_TRY(fb_read_back(e.data() + (size_t)w * nc, p->scratch, (size_t)nc * sizeof(double), s));
         }
-        if (p->pk_geom.size() >= 16) p->pk_geom.erase(p->pk_geom.begin());
-        p->pk_geom.push_back(std::move(e));
-        geo = &p->pk_geom.back();
+        geo = p->pk_geom.insert(key, std::move(e));
     }
     int r = FB_DISPATCH(p, pk_launch<float>(p, false, 0, half1, half2, a, p->scratch, s),
                         pk_launch<double>(p, false, 0, half1, half2, a, p->scratch, s));
     if (r) return r;
     std::vector<double> sums((size_t)nl * nc);
-    FB_HIP(hipMemcpyAsync(sums.data(), p->scratch, sums.size() * sizeof(double), hipMemcpyDeviceToHost, s));
-    FB_HIP(hipStreamSynchronize(s));
-    std::copy(geo->begin() + key.size(), geo->end(), out_host);
+    FB_TRY(fb_read_back(sums.data(), p->scratch, sums.size() * sizeof(double), s));
+    std::copy(geo->begin(), geo->end(), out_host);
     // P = (Lx Ly Lz / N^6) Re(conj(D_1) D_2)
     const double n3 = (double)p->N * p->N * p->N;
     const double scale = (p->L[0] * p->L[1] * p->L[2]) / (n3 * n3);

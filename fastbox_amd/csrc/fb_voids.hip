@@ -431,30 +431,20 @@ __global__ __launch_bounds__(256) void k_stack_finish(const double* psum, const 
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------
-int ensure_small(fb_plan* p) {
-    if (!p->void_small) FB_HIP(hipMalloc(&p->void_small, FB_VOID_SMALL));
-    return FB_OK;
-}
-int ensure_work(fb_plan* p, size_t bytes) { return ensure_bytes(&p->void_work, &p->void_work_cap, bytes); }
-unsigned* small_flag(fb_plan* p) { return (unsigned*)p->void_small; }
-unsigned* small_err(fb_plan* p) { return (unsigned*)p->void_small + 1; }
-double* small_bound(fb_plan* p) { return (double*)p->void_small + 1; }
-double* small_part(fb_plan* p) { return (double*)p->void_small + 8; }      // [FB_VOID_RED_BLOCKS]
-int read_u32(const unsigned* dev, unsigned* host, hipStream_t s) {
-    FB_HIP(hipMemcpyAsync(host, dev, sizeof(unsigned), hipMemcpyDeviceToHost, s));
-    FB_HIP(hipStreamSynchronize(s));
-    return FB_OK;
-}
+unsigned* small_flag(fb_plan* p) { return p->void_small.as<unsigned>(); }
+unsigned* small_err(fb_plan* p) { return p->void_small.as<unsigned>() + 1; }
+double* small_bound(fb_plan* p) { return p->void_small.as<double>() + 1; }
+double* small_part(fb_plan* p) { return p->void_small.as<double>() + 8; }      // [FB_VOID_RED_BLOCKS]
 
 template <typename T>
 int watershed(fb_plan* p, const void* field, int kind, double thr, const void* mask, unsigned* par, int64_t* nreg, hipStream_t s) {
     const int N = p->N;
     const unsigned long long n = (unsigned long long)N * N * N;
     const unsigned long long nb = (n + FB_VOID_TILE - 1) / FB_VOID_TILE;
-    int r = ensure_small(p);
-    if (!r) r = ensure_work(p, (size_t)(2 * nb + 1 + scan_chunks(nb)) * 4);
+    int r = p->void_small.ensure(FB_VOID_SMALL);
+    if (!r) r = p->void_work.ensure((size_t)(2 * nb + 1 + scan_chunks(nb)) * 4);
     if (r) return r;
-    unsigned* cnt = (unsigned*)p->void_work;             // [nb]
+    unsigned* cnt = p->void_work.as<unsigned>();         // [nb]
     unsigned* off = cnt + nb;                            // [nb + 1]: the scan of cnt, off[nb] = the number of minima (totals below 2^31)
     unsigned* csum = off + nb + 1;
     unsigned* flag = small_flag(p);
@@ -471,8 +461,7 @@ int watershed(fb_plan* p, const void* field, int kind, double thr, const void* m
         hipLaunchKernelGGL(k_ws_jump, dim3(grid_for(n, p)), dim3(256), 0, s, par, n, flag);
         FB_LAUNCH_CHECK("k_ws_jump");
         unsigned h = 0;
-        r = read_u32(flag, &h, s);
-        if (r) return r;
+        FB_TRY(fb_read_back(&h, flag, sizeof(unsigned), s));
         if (!h) break;
     }
     hipLaunchKernelGGL(k_ws_count, dim3((unsigned)nb), dim3(256), 0, s, (const unsigned*)par, n, cnt);
@@ -484,8 +473,7 @@ int watershed(fb_plan* p, const void* field, int kind, double thr, const void* m
     hipLaunchKernelGGL(k_ws_label, dim3(grid_for(n, p)), dim3(256), 0, s, par, n);
     FB_LAUNCH_CHECK("k_ws_label");
     unsigned tot = 0;
-    r = read_u32(off + nb, &tot, s);
-    if (r) return r;
+    FB_TRY(fb_read_back(&tot, off + nb, sizeof(unsigned), s));
     *nreg = (int64_t)tot;
     return FB_OK;
 }
@@ -494,10 +482,10 @@ template <typename T>
 int region_stats(fb_plan* p, const int* lab, int64_t nl, const void* field, void* out, int* bad, hipStream_t s) {
     const int N = p->N;
     const unsigned long long n = (unsigned long long)N * N * N, n1 = (unsigned long long)nl + 1;
-    int r = ensure_small(p);
-    if (!r) r = ensure_work(p, (size_t)16 * n1 * 8);
+    int r = p->void_small.ensure(FB_VOID_SMALL);
+    if (!r) r = p->void_work.ensure((size_t)16 * n1 * 8);
     if (r) return r;
-    unsigned long long* acc = (unsigned long long*)p->void_work;
+    unsigned long long* acc = p->void_work.as<unsigned long long>();
     const T* f = (const T*)field;
     FB_HIP(hipMemsetAsync(small_err(p), 0, sizeof(unsigned), s));
     hipLaunchKernelGGL(k_rs_init, dim3(grid_for(16 * n1, p)), dim3(256), 0, s, acc, n1);
@@ -518,8 +506,7 @@ int region_stats(fb_plan* p, const int* lab, int64_t nl, const void* field, void
                        (const double*)small_bound(p), f ? 1 : 0, out);
     FB_LAUNCH_CHECK("k_rs_finish");
     unsigned e = 0;
-    r = read_u32(small_err(p), &e, s);
-    if (r) return r;
+    FB_TRY(fb_read_back(&e, small_err(p), sizeof(unsigned), s));
     *bad = (int)e;
     return FB_OK;
 }
@@ -527,10 +514,10 @@ int region_stats(fb_plan* p, const int* lab, int64_t nl, const void* field, void
 int merge_regions(fb_plan* p, const int* lab, int64_t nl, const double* mean, double thr, int* out, int64_t* nmerged, hipStream_t s) {
     const int N = p->N;
     const unsigned long long n = (unsigned long long)N * N * N, n1 = (unsigned long long)nl + 1;
-    int r = ensure_small(p);
-    if (!r) r = ensure_work(p, (size_t)(3 * n1 + 1 + scan_chunks(n1)) * 4);
+    int r = p->void_small.ensure(FB_VOID_SMALL);
+    if (!r) r = p->void_work.ensure((size_t)(3 * n1 + 1 + scan_chunks(n1)) * 4);
     if (r) return r;
-    unsigned* comp = (unsigned*)p->void_work;
+    unsigned* comp = p->void_work.as<unsigned>();
     unsigned* flags = comp + n1;
     unsigned* rank = flags + n1;                         // [n1 + 1]: the scan of flags, rank[n1] = the number of merged regions
     unsigned* csum = rank + n1 + 1;
@@ -547,8 +534,7 @@ int merge_regions(fb_plan* p, const int* lab, int64_t nl, const double* mean, do
         hipLaunchKernelGGL(k_mg_hook, dim3(grid_for(n, p)), dim3(256), 0, s, lab, n, N, n1, mean, thr, comp, changed); }
         FB_LAUNCH_CHECK("k_mg_hook");
         unsigned h = 0;
-        r = read_u32(changed, &h, s);
-        if (r) return r;
+        FB_TRY(fb_read_back(&h, changed, sizeof(unsigned), s));
         if (!h) break;
         for (int jump = 0;; ++jump) {
             if (jump == FB_VOID_MAX_JUMPS) {
@@ -558,8 +544,7 @@ int merge_regions(fb_plan* p, const int* lab, int64_t nl, const double* mean, do
             FB_HIP(hipMemsetAsync(changed, 0, sizeof(unsigned), s));
             hipLaunchKernelGGL(k_mg_jump, dim3(grid_for(n1, p)), dim3(256), 0, s, comp, n1, changed);
             FB_LAUNCH_CHECK("k_mg_jump");
-            r = read_u32(changed, &h, s);
-            if (r) return r;
+            FB_TRY(fb_read_back(&h, changed, sizeof(unsigned), s));
             if (!h) break;
         }
     }
@@ -572,8 +557,7 @@ int merge_regions(fb_plan* p, const int* lab, int64_t nl, const double* mean, do
     hipLaunchKernelGGL(k_mg_relabel, dim3(grid_for(n, p)), dim3(256), 0, s, lab, n, n1, (const unsigned*)flags, out);
     FB_LAUNCH_CHECK("k_mg_relabel");
     unsigned tot = 0;
-    r = read_u32(rank + n1, &tot, s);
-    if (r) return r;
+    FB_TRY(fb_read_back(&tot, rank + n1, sizeof(unsigned), s));
     *nmerged = (int64_t)tot;
     return FB_OK;
 }
@@ -586,10 +570,9 @@ int stack_voids(fb_plan* p, const int* lab, const void* field, const int* vl, co
     const long long chunk = std::max<long long>(1, (nv + nch - 1) / nch);
     const int nc = (int)std::max<long long>(1, (nv + chunk - 1) / chunk);
     const size_t offc = ((size_t)nc * P * 8 + 255) / 256 * 256;
-    int r = ensure_work(p, offc + (size_t)nc * P * 4);
-    if (r) return r;
-    double* psum = (double*)p->void_work;
-    unsigned* pcnt = (unsigned*)((char*)p->void_work + offc);
+    FB_TRY(p->void_work.ensure(offc + (size_t)nc * P * 4));
+    double* psum = p->void_work.as<double>();
+    unsigned* pcnt = (unsigned*)(p->void_work.as<char>() + offc);
     FB_HIP(hipMemsetAsync(hit, 0, (size_t)std::max<long long>(nv, 1) * sizeof(int), s));
     { FbProfScope _ps(p, FBK_REALOP, s);
     hipLaunchKernelGGL((k_stack<T>), dim3((unsigned)((P + 255) / 256), (unsigned)nc), dim3(256), 0, s, lab, (const T*)field, p->N, vl,

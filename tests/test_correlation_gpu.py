@@ -158,6 +158,21 @@ def test_box_state_is_untouched():
 
 
 @pytest.mark.parametrize("prec", ["f64", "f32"])
+def test_bin_geometry_is_recomputed_after_eviction(prec):
+    """The plan keeps the data-independent sums (cells, mean separation) of the last 16 edge sets: after 17 other sets the
+    first one is computed again, and the whole result -- counts and mean separations included -- is what it was."""
+    box = _box(32, 1e3, prec)
+    d1 = box.realise_density(inplace=False)
+    first = box.correlation_function(delta_x=d1, dr=40., rmax=400., poles=[0, 2])
+    for q in range(17):
+        box.correlation_function(delta_x=d1, dr=41. + q, rmax=400.)
+    again = box.correlation_function(delta_x=d1, dr=40., rmax=400., poles=[0, 2])
+    assert np.all(first[2] > 0)                                               # no empty bin: nothing is NaN
+    for x, y in zip(first, again):
+        assert np.array_equal(x, y)
+
+
+@pytest.mark.parametrize("prec", ["f64", "f32"])
 def test_identities(prec):
     box = _box(64, 1e3, prec)
     dx = box.realise_density()

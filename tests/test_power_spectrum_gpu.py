@@ -181,6 +181,22 @@ def test_identities(prec):
         assert np.array_equal(x, y, equal_nan=True)
 
 
+@pytest.mark.parametrize("prec", ["f64", "f32"])
+def test_bin_geometry_is_recomputed_after_eviction(prec):
+    """The plan keeps the data-independent sums (modes, mean |k|, mean mu per cell) of the last 16 (edges, Nmu) sets: after 17
+    other sets the first one is computed again, and the whole result is what it was (NaN where a cell holds no mode)."""
+    box = _box(32, 1e3, prec)
+    d1 = box.realise_density(inplace=False)
+    kf = 2. * np.pi / 1e3
+    first = box.power_spectrum(delta_x=d1, mode="2d", kbins=np.arange(0.5 * kf, 16. * kf, kf), Nmu=5)
+    for q in range(17):                        # 17 distinct sets: the edges differ in all of them, Nmu in most
+        box.power_spectrum(delta_x=d1, mode="2d", kbins=np.arange(0.5 * kf, 16. * kf, (1.1 + 0.05 * q) * kf), Nmu=3 + q % 5)
+    again = box.power_spectrum(delta_x=d1, mode="2d", kbins=np.arange(0.5 * kf, 16. * kf, kf), Nmu=5)
+    assert first[3].sum() > 0 and np.array_equal(first[3], again[3])
+    for x, y in zip(first, again):
+        assert np.array_equal(x, y, equal_nan=True)
+
+
 @pytest.mark.parametrize("prec", ["f32", "f64"])
 def test_lazy_inputs_equal_materialised(prec):
     box = _box(64, 1e3, prec)                  # (64: the size from which f32 boxes defer the redshift-space remap)
