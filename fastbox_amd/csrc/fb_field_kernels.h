@@ -1249,7 +1249,9 @@ __global__ __launch_bounds__(256) void k_sky_fg_cube(const T* __restrict__ amps,
         out[row * N + z] = v;
     }
 }
-// noise.py:72-74: unit normals scaled per frequency channel; device RNG: 4 consecutive channels per call
+// noise.py:72-74: unit normals scaled per frequency channel; device RNG: call q of stream 4 supplies the flat elements
+// 4 q .. 4 q + 3.  Element e lies in channel e mod N: where N mod 4 = 2 every second line of sight starts in the middle
+// of a group, so the channel wraps inside the group (N >= 4: at most once)
 template <typename T>
 __global__ __launch_bounds__(256) void k_sky_noise_cube(const T* __restrict__ unit, const double* __restrict__ sigma,
                                                         T* __restrict__ out, long long n4, int N, RngKey key) {
@@ -1260,7 +1262,10 @@ __global__ __launch_bounds__(256) void k_sky_noise_cube(const T* __restrict__ un
     else stream_normals4<T>((unsigned long long)q, 4u, key, g[0], g[1], g[2], g[3]);
     const int z0 = (int)((4 * q) % N);
 #pragma unroll
-    for (int u = 0; u < 4; ++u) out[4 * q + u] = (T)((double)g[u] * sigma[z0 + u]);
+    for (int u = 0; u < 4; ++u) {
+        const int z = z0 + u < N ? z0 + u : z0 + u - N;
+        out[4 * q + u] = (T)((double)g[u] * sigma[z]);
+    }
 }
 
 // real cube -> complex cube (imaginary part 0); complex cube *= mask2d[k_x][k_y] (filters.py:79-89)

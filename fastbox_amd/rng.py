@@ -118,6 +118,25 @@ def los_noise(N, seed, dtype=np.float64):
     return stream_normals(N ** 3, 1, seed, 0, dtype).reshape(N, N, N)
 
 
+def sky_map_noise(N, seed, dtype=np.float64):
+    """(re, im), each (N, N), of the foreground amplitude map (k_sky_colour_map, stream 2): element q = x N + y takes
+    normals 2 q and 2 q + 1 of the stream -- call q >> 1, words (0, 1) for even q and (2, 3) for odd q.  `seed`:
+    sky.sky_draw_seed(box seed, number of the draw)."""
+    g = stream_normals(2 * N * N, 2, seed, 0, dtype).reshape(N, N, 2)
+    return np.ascontiguousarray(g[:, :, 0]), np.ascontiguousarray(g[:, :, 1])
+
+
+def sky_index_noise(N, seed, dtype=np.float64):
+    """(N, N) unit normals of the spectral-index map (k_sky_normal_map): the first N^2 normals of stream 3."""
+    return stream_normals(N * N, 3, seed, 0, dtype).reshape(N, N)
+
+
+def sky_noise_normals(N, seed, dtype=np.float64):
+    """(N, N, N) unit normals of the radiometer noise cube (k_sky_noise_cube): the first N^3 normals of stream 4; call q
+    supplies the flat elements 4 q .. 4 q + 3, whose channels are (4 q + u) mod N."""
+    return stream_normals(N ** 3, 4, seed, 0, dtype).reshape(N, N, N)
+
+
 def gcr_normals(N, which, seed, realisation=0):
     """The unit normals of the constrained realisations (fb_inpaint.hip): which = 1, 2, 3 for omega1, omega2, omega3 on streams
     7, 8, 9; element p N + c of the stream belongs to line of sight p, channel c.  Always fp64.  Returns (N^2, N)."""

@@ -30,6 +30,12 @@ def _gaussian_weights(sigma, truncate=4.0):
     return np.ascontiguousarray(phi / phi.sum()), radius
 
 
+def sky_draw_seed(box_seed, draw):
+    """Seed of the draw-th (1, 2, ...) sky draw of a box with rng='device': what the foreground map (stream 2), the
+    spectral-index map (3) and the noise cube (4) key the counter generator with; host models in fastbox_amd/rng.py."""
+    return (int(box_seed) * 0x9E3779B97F4A7C15 + 0xD1B54A32D192ED03 * int(draw)) & (2 ** 64 - 1)
+
+
 class _Maps(object):
     """Device helpers shared by the two models: N x N maps in the plan's precision."""
 
@@ -62,7 +68,7 @@ class _Maps(object):
     def next_seed(self):
         b = self.box
         b._sky_draws = getattr(b, "_sky_draws", 0) + 1
-        return (b.seed * 0x9E3779B97F4A7C15 + 0xD1B54A32D192ED03 * b._sky_draws) & (2 ** 64 - 1)
+        return sky_draw_seed(b.seed, b._sky_draws)
 
 
 class ForegroundModel(object):
