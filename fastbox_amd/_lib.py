@@ -115,6 +115,11 @@ SIGNATURES = {
     "fb_pair_work_bytes": (c_i64, [c_i64, c_i64, c_i64]),
     "fb_pair_count": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, c_i64, c_int, P_double, c_int, c_int, c_double, P_i32, c_void_p,
                               c_i64, c_void_p, P_i32, P_double, c_void_p]),
+    "fb_profile_work_bytes": (c_i64, [c_i64, c_i64, c_int]),
+    "fb_profile_bin": (c_int, [c_void_p, c_void_p, c_i64, c_void_p, P_i32, c_void_p, c_i64, P_i32, P_double, c_void_p]),
+    "fb_halo_profiles": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, P_double, c_int, c_void_p, P_i32, c_void_p]),
+    "fb_halo_apertures": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  P_i32, c_void_p]),
     "fb_real_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_void_p]),
     "fb_real_multiply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fb_real_to_complex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -1180,6 +1180,20 @@ class CosmoBox(object):
         from . import halos
         return halos.pair_counts(self, first, second=second, edges=edges, mode=mode, Nmu=Nmu, pimax=pimax, poles=poles)
 
+    def halo_profiles(self, centres, particles, edges, **kw):
+        """Additive: radial profiles of all particles around given centres (a ``FoFHalos``, another HaloCatalogue or a host
+        (nh, 3) array), counted on the device: a ``HaloProfiles`` of integer counts per bin, enclosed counts and densities.
+        Keywords and definition: ``fastbox_amd.halos.halo_profiles``; DESIGN.md section 4."""
+        from . import halos
+        return halos.halo_profiles(self, centres, particles, edges, **kw)
+
+    def spherical_overdensity(self, centres, particles, **kw):
+        """Additive: spherical-overdensity radii R_Delta and masses M_Delta around given centres, with the exact members,
+        centre of mass, mean velocity and velocity dispersion inside R_Delta, as an ``SOHalos`` catalogue (its positions are
+        the centres).  Keywords and definition: ``fastbox_amd.halos.spherical_overdensity``; DESIGN.md section 4."""
+        from . import halos
+        return halos.spherical_overdensity(self, centres, particles, **kw)
+
     def sigmaR(self, R):
         """RMS of the field smoothed with a top-hat of R Mpc/h, from the binned power
         spectrum (box.py:657-683; scipy's simps is spelled simpson since 1.14)."""

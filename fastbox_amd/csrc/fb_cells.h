@@ -1,7 +1,8 @@
-// Cell binning of a periodic particle set, shared by the friends-of-friends search (fb_fof.hip) and the pair counts
-// (fb_pairs.hip): minimum-image differences, the cell of a particle, the occupancy histogram, the permuted copy of the wrapped
-// positions and the list of the further tiles of crowded cells.  The wrap itself is wrap_pos of fb_dev.h, the scan of the
-// histogram is exscan of fb_scan.h (both included here).
+// Cell binning of a periodic particle set, shared by the friends-of-friends search (fb_fof.hip), the pair counts
+// (fb_pairs.hip) and the halo profiles (fb_profiles.hip): minimum-image differences, the cell of a particle, the occupancy
+// histogram, the permuted copy of the wrapped positions, the list of the further tiles of crowded cells and the largest |v|
+// of a velocity array.  The wrap itself is wrap_pos of fb_dev.h, the scan of the histogram is exscan of fb_scan.h (both
+// included here).
 //
 // No contraction: the wrapped positions and the minimum-image differences must be the doubles of the numpy statements
 // (tests/fof_numpy.py, tests/pairs_numpy.py).  The pragma below is at file scope on purpose: it switches contraction off for
@@ -17,6 +18,7 @@
 
 #define FB_FOF_TILE 64                   // particles per LDS tile = lanes per workgroup of the pair search (FOF_TILE of halos.py)
 #define FB_FOF_ERR_POS 1u                // error word: a position that is not finite, or too large to wrap into the box
+#define FB_FOF_ERR_VEL 4u                // error word: a velocity that is not finite
 #define FB_FOF_NONE 0xFFFFFFFFu
 #define FB_FOF_WRAP_MAX 4503599627370496.0   // 2^52: positions must satisfy |x| < 2^52 L
 
@@ -83,6 +85,19 @@ __global__ __launch_bounds__(256) void k_fof_items(const unsigned* start, unsign
             items[2ull * slot + 1] = k;
         }
     }
+}
+
+// max |v| over all components (the bit pattern of a non-negative double orders as an integer)
+__global__ __launch_bounds__(256) void k_fof_vmax(const double* vel, unsigned long long n3, unsigned long long* vmax_bits, unsigned* err) {
+    double m = 0.0;
+    bool bad = false;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n3; i += (unsigned long long)gridDim.x * 256) {
+        const double a = fabs(vel[i]);
+        if (!(a < INFINITY)) bad = true; else m = fmax(m, a);
+    }
+    m = wave_max(m);
+    if ((threadIdx.x & 63) == 0) atomicMax(vmax_bits, (unsigned long long)__double_as_longlong(m));
+    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(err, FB_FOF_ERR_VEL);
 }
 
 // ---- host ---------------------------------------------------------------------------------------------------------------

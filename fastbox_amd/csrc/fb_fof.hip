@@ -15,8 +15,7 @@
 
 #define FB_FOF_SMALL 256                 // bytes at the head of every work buffer: the words below
 #define FB_FOF_MAX_JUMPS 40              // pointer-jumping rounds of the flattening (path lengths halve: 2^31 particles need 32)
-#define FB_FOF_ERR_LOOP 2u               // error word (FB_FOF_ERR_POS = 1 is in fb_cells.h): a find or union loop hit its cap
-#define FB_FOF_ERR_VEL 4u                //                                                   a velocity that is not finite
+#define FB_FOF_ERR_LOOP 2u               // error word (FB_FOF_ERR_POS = 1 and FB_FOF_ERR_VEL = 4 are in fb_cells.h): a loop hit its cap
 
 namespace {
 
@@ -158,18 +157,6 @@ __global__ __launch_bounds__(256) void k_fof_label(const unsigned* root, unsigne
         const unsigned r = root[i];
         if (r != (unsigned)i) labels[i] = labels[r];
     }
-}
-// max |v| over all components (the bit pattern of a non-negative double orders as an integer)
-__global__ __launch_bounds__(256) void k_fof_vmax(const double* vel, unsigned long long n3, unsigned long long* vmax_bits, unsigned* err) {
-    double m = 0.0;
-    bool bad = false;
-    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n3; i += (unsigned long long)gridDim.x * 256) {
-        const double a = fabs(vel[i]);
-        if (!(a < INFINITY)) bad = true; else m = fmax(m, a);
-    }
-    m = wave_max(m);
-    if ((threadIdx.x & 63) == 0) atomicMax(vmax_bits, (unsigned long long)__double_as_longlong(m));
-    if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(err, FB_FOF_ERR_VEL);
 }
 // Fixed point in two 64-bit accumulators (fb_dev.h): the sums do not depend on the order of the particles.  F = 93 - e with
 // (number of particles) (bound of |x|) < 2^e: hi stays below 2^61.

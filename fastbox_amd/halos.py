@@ -611,6 +611,331 @@ def pair_counts(box, first, second=None, edges=None, mode='1d', Nmu=10, pimax=No
     return PairCounts(e, npairs, L, n1, n2, auto, mode=mode, poles=poles)
 
 
+# ---------------------------------------------------------------------- radial profiles and spherical-overdensity masses
+PROFILE_MAX_NR = 256                # FB_PROF_MAX_NR of fb_profiles.hip
+SO_RMAX = 5.                        # Mpc: the default outer edge of spherical_overdensity
+
+
+class HaloProfiles(object):
+    """Radial profiles of all particles around given centres (``halo_profiles``).  Members: ``edges``
+    (nr + 1, Mpc); ``r``, the arithmetic bin midpoints; ``counts`` int64 (nh, nr): particles with edges[b]^2 <= d^2 <
+    edges[b + 1]^2; ``inner`` int64 (nh,): particles with d^2 < edges[0]^2; ``enclosed`` int64 (nh, nr + 1): N(< edges[j]) =
+    inner + sum_{b < j} counts; ``density`` (nh, nr): particle_mass counts / (4 pi / 3 (e1^3 - e0^3)), Msun / Mpc^3;
+    ``enclosed_density`` (nh, nr + 1): particle_mass N(< e_j) / (4 pi / 3 e_j^3), NaN at an edge of 0; ``particle_mass``."""
+
+    def __init__(self, edges, inner, counts, particle_mass):
+        self.edges = np.array(edges, dtype=np.float64)
+        self.inner = np.array(inner, dtype=np.int64)
+        self.counts = np.array(counts, dtype=np.int64).reshape(self.inner.size, self.edges.size - 1)
+        self.particle_mass = float(particle_mass)
+        e = self.edges
+        self.r = 0.5 * (e[1:] + e[:-1])
+        self.enclosed = np.concatenate([self.inner[:, None], self.inner[:, None] + np.cumsum(self.counts, axis=1)], axis=1)
+        self.density = self.particle_mass * self.counts / ((4. * np.pi / 3.) * (e[1:] ** 3 - e[:-1] ** 3))[None, :]
+        with np.errstate(divide='ignore', invalid='ignore'):
+            self.enclosed_density = np.where(e > 0., self.particle_mass * self.enclosed / ((4. * np.pi / 3.) * e ** 3)[None, :], np.nan)
+
+    def __len__(self):
+        return self.inner.size
+
+    def __repr__(self):
+        return "HaloProfiles(%d centres, %d bins)" % (self.inner.size, self.edges.size - 1)
+
+
+class SOHalos(HaloCatalogue):
+    """The spherical-overdensity halos of ``spherical_overdensity``: a HaloCatalogue whose positions are the input centres
+    -- ``paint_catalogue`` and ``pair_counts`` take it -- with, per centre, ``radius`` (R_Delta, Mpc), ``mass`` (M_Delta =
+    4 pi / 3 Delta rho_ref R^3, Msun) and ``status`` (0: found; 1: nowhere above the threshold; 2: still above it at the last
+    edge; radius and mass are NaN unless 0), ``count`` (int64: the particles with d^2 < R^2 exactly; 0 unless status 0),
+    ``com`` (a HaloCatalogue: their centre of mass, NaN where count is 0), ``velocities`` (a HaloCatalogue of their mean
+    velocity) and ``sigma_v`` (host, km/s: the 1-d dispersion), both None without particle velocities, ``profiles`` (the
+    ``HaloProfiles`` behind the radii), ``delta``, ``rho_ref`` (comoving Msun / Mpc^3) and ``particle_mass``."""
+
+    def __init__(self, engine, buf, n, radius, mass, status, count, com, velocities, sigma_v, profiles, delta, rho_ref):
+        HaloCatalogue.__init__(self, engine, buf, n)
+        self.radius, self.mass, self.status, self.count = radius, mass, status, count
+        self.com, self.velocities, self.sigma_v, self.profiles = com, velocities, sigma_v, profiles
+        self.delta, self.rho_ref, self.particle_mass = float(delta), float(rho_ref), profiles.particle_mass
+
+    def __repr__(self):
+        return "SOHalos(%d centres, %d with a radius, Delta = %g)" % (self.n, int(np.count_nonzero(self.status == 0)), self.delta)
+
+
+def so_reference_density(box, reference='mean'):
+    """rho_ref of ``spherical_overdensity``, comoving, in Msun / Mpc^3: 'mean': Omega_m 2.77536627e11 h^2; 'crit': the
+    critical density at the box redshift, 2.77536627e11 h^2 E(a)^2 a^3; or a positive number, taken as it is."""
+    h2 = float(box.cosmo['h']) ** 2
+    if isinstance(reference, str):
+        if reference == 'mean':
+            return (box.cosmo['Omega_c'] + box.cosmo['Omega_b']) * RHO_CRIT * h2
+        if reference == 'crit':
+            from .box import _ccl
+            a = float(box.scale_factor)
+            return RHO_CRIT * h2 * float(_ccl.h_over_h0(box.cosmo, a)) ** 2 * a ** 3
+        raise ValueError("reference: 'mean', 'crit' or a density in Msun / Mpc^3")
+    rho = float(reference)
+    if not (np.isfinite(rho) and rho > 0.):
+        raise ValueError("reference: 'mean', 'crit' or a positive density in Msun / Mpc^3")
+    return rho
+
+
+def so_from_enclosed(edges, enclosed, particle_mass, rho_ref, delta):
+    """(radius, mass, status) from enclosed counts: pure numpy, no device.  ``enclosed`` (nh, nr + 1): N(< edges[j]).
+    rho_j = particle_mass N(< e_j) / (4 pi / 3 e_j^3) at every edge e_j > 0; j* = the largest j with rho_j >= delta rho_ref
+    -- the outermost crossing, on purpose: a single inner bin with one particle is noisy, and the first down-crossing stops
+    there.  status 1: no such j; 2: j* is the last edge; both give NaN.  status 0: R is the log-log linear interpolation of
+    (e, rho) between j* and j* + 1 at rho = delta rho_ref, and M = 4 pi / 3 delta rho_ref R^3."""
+    e = np.asarray(edges, dtype=np.float64)
+    N = np.asarray(enclosed, dtype=np.float64).reshape(-1, e.size)
+    nh, nr = N.shape[0], e.size - 1
+    thr = float(delta) * float(rho_ref)
+    pos = e > 0.
+    rho = np.zeros_like(N)
+    rho[:, pos] = float(particle_mass) * N[:, pos] / ((4. * np.pi / 3.) * e[pos] ** 3)[None, :]
+    above = (rho >= thr) & pos[None, :]
+    any_above = above.any(axis=1)
+    jstar = nr - np.argmax(above[:, ::-1], axis=1)                    # the last True of each row (meaningless without one)
+    status = np.where(~any_above, 1, np.where(jstar == nr, 2, 0)).astype(np.int64)
+    radius = np.full(nh, np.nan)
+    ok = np.nonzero(status == 0)[0]
+    if ok.size:
+        j = jstar[ok]
+        le0, le1 = np.log(e[j]), np.log(e[j + 1])
+        lr0, lr1 = np.log(rho[ok, j]), np.log(rho[ok, j + 1])         # rho_j >= thr > rho_{j + 1} > 0: N does not decrease
+        radius[ok] = np.clip(np.exp(le0 + (np.log(thr) - lr0) * (le1 - le0) / (lr1 - lr0)), e[j], e[j + 1])   # rounding stays inside
+    mass = (4. * np.pi / 3.) * thr * radius ** 3
+    return radius, mass, status
+
+
+def profile_edges(L, edges):
+    """The checked radial edges of ``halo_profiles``: strictly ascending, finite, edges[0] >= 0, at most 256 bins, the last
+    edge below min(L) / 2.  ValueError otherwise."""
+    e = np.array(edges, dtype=np.float64)
+    if e.ndim != 1 or e.size < 2 or not np.all(np.isfinite(e)) or e[0] < 0. or not np.all(e[1:] > e[:-1]):
+        raise ValueError("edges: a strictly ascending array of at least 2 finite values, edges[0] >= 0")
+    if e.size - 1 > PROFILE_MAX_NR:
+        raise ValueError("edges: at most %d bins, got %d" % (PROFILE_MAX_NR, e.size - 1))
+    if not e[-1] < 0.5 * min(L):
+        raise ValueError("edges: the last edge %.6g Mpc must be below half the shortest box side (%.6g Mpc)" % (e[-1], 0.5 * min(L)))
+    return e
+
+
+def profile_device_bytes(n, nh, cells, nr=PROFILE_MAX_NR, velocities=False, host_particles=False, host_centres=False):
+    """Device bytes halo_profiles and spherical_overdensity allocate beside the particles and centres: the work buffer (28
+    bytes a particle -- the permuted positions and cell ids -- and 28 more with velocities: their permuted copy and the
+    permutation), the (nh, nr + 1) counts, the aperture outputs (radii, counts, centres of mass, mean velocities,
+    dispersions) and the uploads of host inputs."""
+    ncells = int(cells[0]) * int(cells[1]) * int(cells[2])
+    need = int(_lib.load().fb_profile_work_bytes(int(n), ncells, 1 if velocities else 0)) + 4 * nh * (nr + 1) + (8 + 4 + 24 + 24 + 8) * nh + 512
+    if host_particles:
+        need += (24 * n + 32) * (2 if velocities else 1)
+    return need + (24 * nh + 32 if host_centres else 0)
+
+
+class _CentreSweeps(object):
+    """The particles of one call binned once on the device (fb_profile_bin), for the profile sweep and the aperture sweep."""
+
+    def __init__(self, box, who, centres, particles, velocities, reach, nr, timings):
+        import time
+        self.eng = eng = box.engine
+        self.who, self.timings, self.time = who, timings, time
+        self.L = L = (float(box.Lx), float(box.Ly), float(box.Lz))
+        self.keep = keep = []
+        self.nh, hc, cc = _pair_positions(eng, centres, "centres")
+        vhost = vcat = None
+        if isinstance(particles, HaloCatalogue):
+            if particles.engine is not eng:
+                raise ValueError("particles: a catalogue of this box")
+            if velocities is not None:
+                raise ValueError("velocities: only with host positions (a ColaParticles carries its own)")
+            self.n, hp = particles.n, None
+            vcat = getattr(particles, "velocities", None)
+            vcat = vcat if isinstance(vcat, HaloCatalogue) and vcat.n == self.n else None
+        else:
+            hp = np.ascontiguousarray(particles, dtype=np.float64)
+            if hp.ndim != 2 or hp.shape[1] != 3:
+                raise ValueError("particles: an (n, 3) array")
+            self.n = hp.shape[0]
+            if velocities is not None:
+                vhost = np.ascontiguousarray(velocities, dtype=np.float64)
+                if vhost.shape != hp.shape:
+                    raise ValueError("velocities: expected shape %s, got %s" % (hp.shape, vhost.shape))
+        n, nh = self.n, self.nh
+        if max(n, nh) > 2 ** 31 - 2:
+            raise ValueError("%s: at most 2^31 - 2 particles and as many centres" % who)
+        self.has_vel = vhost is not None or vcat is not None
+        self.reach = float(reach)
+        self.cells = cells = pair_cells(L, (self.reach,) * 3, max(n, 1))
+        need, have = profile_device_bytes(n, nh, cells, nr, self.has_vel, hp is not None, hc is not None), eng.free_bytes()
+        if need > have:
+            raise MemoryError("%s: %d particles in %d x %d x %d cells and %d centres take %.2f GiB of work memory, %.2f GiB are free"
+                              % ((who, n) + cells + (nh, need / 2. ** 30, have / 2. ** 30)))
+
+        def pointer(m, host, cat):
+            if m == 0:
+                return None, None
+            if cat is not None:
+                return cat.ptr, cat._buf
+            keep.append(eng.upload_raw(host))
+            return keep[-1].ptr, keep[-1]
+
+        self.cptr, self.cbuf = pointer(nh, hc, cc)
+        pptr, _ = pointer(n, hp, particles if hp is None else None)
+        vptr, _ = pointer(n if self.has_vel else 0, vhost, vcat)
+        self.wbytes = int(eng.lib.fb_profile_work_bytes(n, cells[0] * cells[1] * cells[2], 1 if self.has_vel else 0))
+        self.work = eng._alloc_bytes(self.wbytes)
+        bad = ctypes.c_int32(0)
+        ms = (ctypes.c_double * 1)()
+        # (with no particle there is no velocity array to point to, and no velocity to check)
+        _lib.call("fb_profile_bin", eng._plan, pptr, n, vptr, (ctypes.c_int32 * 3)(*cells), self.work.ptr, self.wbytes,
+                  ctypes.byref(bad), ms if timings is not None else None, eng.stream)
+        eng.sync()                          # host arrays behind the uploads must outlive the copies
+        self.binned_vel = self.has_vel and n > 0
+        if bad.value & 1:
+            raise ValueError("%s: a position is not finite, or too large to wrap into the box" % who)
+        if bad.value:
+            raise ValueError("%s: a velocity is not finite, or n max |v|^2 overflows" % who)
+        if timings is not None:
+            timings.update(bin_ms=ms[0], cells=cells)
+
+    def _bad(self, bad):
+        if bad.value & 1:
+            raise ValueError("%s: a centre is not finite, or too large to wrap into the box" % self.who)
+        if bad.value:
+            raise ValueError("%s: an aperture beyond the reach of the cells" % self.who)
+
+    def profiles(self, e):
+        """(nh, nr + 1) int64: column 0 the particles inside edges[0], then the bins."""
+        eng, nh, ncol = self.eng, self.nh, e.size
+        rows = np.zeros((nh, ncol), dtype=np.uint32)
+        if nh:
+            t0 = self.time.perf_counter()
+            out = eng._alloc_bytes(rows.nbytes)
+            e2 = np.ascontiguousarray(e * e)
+            bad = ctypes.c_int32(0)
+            _lib.call("fb_halo_profiles", eng._plan, self.work.ptr, self.cptr, nh, e2.ctypes.data_as(ctypes.POINTER(ctypes.c_double)),
+                      ncol - 1, out.ptr, ctypes.byref(bad), eng.stream)
+            self._bad(bad)
+            if self.timings is not None:
+                self.timings["profile_ms"] = 1e3 * (self.time.perf_counter() - t0)
+            _lib.call("fb_memcpy_d2h", rows.ctypes.data_as(ctypes.c_void_p), out.ptr, rows.nbytes, eng.stream)
+            eng.sync()
+        return rows.astype(np.int64)
+
+    def apertures(self, r2):
+        """(count int64 (nh,), com buffer, vmean buffer or None, sigma (nh,) or None) of the particles with d^2 < r2."""
+        eng, nh = self.eng, self.nh
+        vel = self.has_vel
+        if not nh:
+            return np.zeros(0, dtype=np.int64), None, None, (np.zeros(0) if vel else None)
+        r2 = np.ascontiguousarray(r2, dtype=np.float64)
+        rbuf = eng.upload_raw(r2)
+        cnt, com = eng._alloc_bytes(4 * nh), eng._alloc_bytes(24 * nh)
+        vm = eng._alloc_bytes(24 * nh) if vel else None
+        sg = eng._alloc_bytes(8 * nh) if vel else None
+        dev_vel = self.binned_vel
+        bad = ctypes.c_int32(0)
+        t0 = self.time.perf_counter()
+        _lib.call("fb_halo_apertures", eng._plan, self.work.ptr, self.cptr, rbuf.ptr, nh, self.reach, cnt.ptr, com.ptr,
+                  vm.ptr if dev_vel else None, sg.ptr if dev_vel else None, ctypes.byref(bad), eng.stream)
+        self._bad(bad)
+        if self.timings is not None:
+            self.timings["aperture_ms"] = 1e3 * (self.time.perf_counter() - t0)
+        count = np.empty(nh, dtype=np.uint32)
+        _lib.call("fb_memcpy_d2h", count.ctypes.data_as(ctypes.c_void_p), cnt.ptr, count.nbytes, eng.stream)
+        sigma = None
+        if vel:
+            sigma = np.full(nh, np.nan)
+            if dev_vel:
+                _lib.call("fb_memcpy_d2h", sigma.ctypes.data_as(ctypes.c_void_p), sg.ptr, sigma.nbytes, eng.stream)
+            else:                           # velocities of no particle: every mean is NaN
+                nanv = np.full((nh, 3), np.nan)
+                _lib.call("fb_memcpy_h2d", vm.ptr, nanv.ctypes.data_as(ctypes.c_void_p), nanv.nbytes, eng.stream)
+        eng.sync()
+        return count.astype(np.int64), com, vm, sigma
+
+
+def _profile_mass(box, n, particle_mass):
+    if particle_mass is not None:
+        return float(particle_mass)
+    return (box.cosmo['Omega_c'] + box.cosmo['Omega_b']) * RHO_CRIT * box.cosmo['h'] ** 2 * float(box.Lx) * float(box.Ly) * float(box.Lz) / n \
+        if n else 0.
+
+
+def halo_profiles(box, centres, particles, edges, particle_mass=None, timings=None):
+    """Radial profiles of the particles around given centres, counted on the device (definition and design in DESIGN.md
+    section 4).  ``centres``: a FoFHalos or other HaloCatalogue of this box, or a host (nh, 3) array; ``particles``: as for
+    ``find_halos_fof``.  Positions are periodic in the box and wrapped on read; d^2 = (dx dx + dy dy) + dz dz on the
+    minimum-image differences.  All particles count, whatever group they belong to, a particle on the centre included.
+    ``edges``: radial edges in Mpc, lower edge inclusive, upper exclusive, decided on squares (``profile_edges``).
+    ``particle_mass``: Msun, default that of ``find_halos_fof``.  ``timings``: a dict that receives the milliseconds of the
+    stages.  Returns a ``HaloProfiles``.  ValueError: bad edges (before the device is touched), a position or centre that is
+    not finite or too large to wrap into the box (|x| >= 2^52 L); MemoryError before any kernel runs if the work memory does
+    not fit."""
+    e = profile_edges((float(box.Lx), float(box.Ly), float(box.Lz)), edges)
+    sw = _CentreSweeps(box, "halo_profiles", centres, particles, None, e[-1], e.size - 1, timings)
+    rows = sw.profiles(e)
+    return HaloProfiles(e, rows[:, 0], rows[:, 1:], _profile_mass(box, sw.n, particle_mass))
+
+
+def halo_apertures(box, centres, particles, radius2, velocities=None, timings=None):
+    """Moments of the particles inside each centre's own sphere, summed on the device: ``radius2`` (nh,) holds the *squared*
+    radii in Mpc^2, a particle is a member iff d^2 < radius2 strictly (so a radius of 0 has no member).  Returns host arrays
+    (count int64 (nh,), com (nh, 3), vmean (nh, 3) or None, sigma_v (nh,) or None): com = wrap(c + sum d / m), vmean =
+    sum v / m, sigma_v = sqrt(max(0, (sum v.v / m - vmean.vmean) / 3)), NaN where m = 0.  The sums are fixed-point: the same
+    bit for bit from call to call and for any order of the particles.  Inputs and errors as ``halo_profiles``; the largest
+    radius must stay below min(L) / 2."""
+    r2 = np.ascontiguousarray(radius2, dtype=np.float64).reshape(-1)
+    nh = centres.n if isinstance(centres, HaloCatalogue) else np.shape(centres)[0]
+    if r2.size != nh or not np.all(np.isfinite(r2)) or np.any(r2 < 0.):
+        raise ValueError("radius2: %d finite squared radii >= 0" % nh)
+    L = (float(box.Lx), float(box.Ly), float(box.Lz))
+    reach = float(np.sqrt(r2.max())) * (1. + 1e-15) if nh else 0.
+    reach = max(reach, 1e-3 * min(L))                    # cells no finer than a thousandth of the box
+    if not reach < 0.5 * min(L):
+        raise ValueError("radius2: the largest radius %.6g Mpc must be below half the shortest box side (%.6g Mpc)" % (reach, 0.5 * min(L)))
+    sw = _CentreSweeps(box, "halo_apertures", centres, particles, velocities, reach, 0, timings)
+    count, com, vm, sigma = sw.apertures(r2)
+    return count, np.array(HaloCatalogue(sw.eng, com, nh)), (np.array(HaloCatalogue(sw.eng, vm, nh)) if sw.has_vel else None), sigma
+
+
+def spherical_overdensity(box, centres, particles, delta=200., reference='mean', rmax=None, nbins=32, rmin=None, edges=None,
+                          particle_mass=None, velocities=None, timings=None):
+    """Spherical-overdensity radii and masses around given centres (definition, design and the differences from nbodykit's
+    conventions in DESIGN.md section 4): the profile of all particles around every centre (``halo_profiles``), R_Delta where
+    the mean enclosed density falls through ``delta`` x rho_ref for the last time (``so_from_enclosed``), M_Delta = 4 pi / 3
+    delta rho_ref R^3, and one more sweep for the particles with d^2 < R^2 exactly: their number, centre of mass, mean
+    velocity and velocity dispersion.  The particles are binned once for both sweeps.  ``reference``: 'mean', 'crit' or a
+    density (``so_reference_density``).  ``edges``: radial edges in Mpc; default ``nbins`` logarithmic bins from ``rmin``
+    (default a quarter of the mean particle spacing, at most rmax / 2) to ``rmax`` (default 5 Mpc -- beyond the virial radius
+    of any cluster -- or 0.45 min(L) in a box too small for that).  A centre still above the threshold at the last edge gets
+    status 2: pass a larger ``rmax``.  ``velocities``: host (n, 3), with host particles only; a ColaParticles brings its own.
+    No unbinding, no recentring.  Returns an ``SOHalos``.  Errors: as ``halo_profiles``, and ValueError for a velocity that is
+    not finite."""
+    L = (float(box.Lx), float(box.Ly), float(box.Lz))
+    delta = float(delta)
+    if not (np.isfinite(delta) and delta > 0.):
+        raise ValueError("delta: a positive number")
+    rho_ref = so_reference_density(box, reference)
+    n = particles.n if isinstance(particles, HaloCatalogue) else np.shape(particles)[0]
+    if edges is None:
+        rmax = min(SO_RMAX, 0.45 * min(L)) if rmax is None else float(rmax)
+        if rmin is None:
+            rmin = min(0.25 * (L[0] * L[1] * L[2] / max(n, 1)) ** (1. / 3.), 0.5 * rmax)
+        if not (0. < float(rmin) < rmax) or int(nbins) < 1:
+            raise ValueError("0 < rmin < rmax and nbins >= 1")
+        edges = np.geomspace(float(rmin), rmax, int(nbins) + 1)
+    e = profile_edges(L, edges)
+    sw = _CentreSweeps(box, "spherical_overdensity", centres, particles, velocities, e[-1], e.size - 1, timings)
+    rows = sw.profiles(e)
+    prof = HaloProfiles(e, rows[:, 0], rows[:, 1:], _profile_mass(box, sw.n, particle_mass))
+    radius, mass, status = so_from_enclosed(e, prof.enclosed, prof.particle_mass, rho_ref, delta)
+    count, com, vm, sigma = sw.apertures(np.where(status == 0, radius * radius, 0.))
+    eng, nh = sw.eng, sw.nh
+    vel = HaloCatalogue(eng, vm, nh) if sw.has_vel else None
+    return SOHalos(eng, sw.cbuf, nh, radius, mass, status, count, HaloCatalogue(eng, com, nh), vel, sigma, prof, delta, rho_ref)
+
+
 def paint(box, positions, weights=None, window='cic', compensated=False):
     """CosmoBox.paint_catalogue: see there."""
     eng, N = box.engine, box.N

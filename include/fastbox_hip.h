@@ -479,6 +479,42 @@ int fb_pair_count(fb_plan* plan, const double* pos1, int64_t n1, const double* p
                   int nr, int nsub, double sub_max, const int* ncell, void* work, int64_t work_bytes, uint64_t* counts_out,
                   int* bad, double* stage_ms, void* stream);
 
+/* ---- radial profiles and aperture moments around given centres (spherical-overdensity halos) ----------
+ * One box on one GPU; particle data are fp64 whatever the plan's precision.  pos, centres: DEVICE double[.][3] in Mpc, periodic
+ * in the plan's box, wrapped on read; d = the minimum-image difference (particle - centre) of the wrapped coordinates exactly
+ * as fb_fof_link and fb_pair_count take it, d^2 = (dx dx + dy dy) + dz dz with every operation rounded on its own.  No square
+ * root is taken in any comparison.  All particles count, a particle that coincides with the centre included (d^2 = 0).
+ * 0 <= n <= 2^31 - 2, 0 <= nh <= 2^31 - 2.
+ * fb_profile_work_bytes: bytes of the work buffer for n particles in ncells cells (-1: bad arguments): 28 n bytes, and 28 n
+ *   more with velocities, beside 8 bytes per cell.
+ * fb_profile_bin: bins the particles once into ncell (HOST int[3]: at least 2 cells per axis, at most 2^31 in all) and leaves
+ *   in `work` the wrapped positions in cell order, the cell table and -- vel (DEVICE double[n][3]) not NULL -- the velocities
+ *   in the same order (a permuted copy), for any number of the two sweeps below.  *bad = 1 if a position is not finite or has
+ *   |x| >= 2^52 L; *bad = 4 if a velocity, or 3 n max|v|^2, is not finite; the buffer is then not prepared.  stage_ms: HOST
+ *   double[1] or NULL: milliseconds of the binning.  Synchronises.
+ * fb_halo_profiles: counts_out (DEVICE uint32[nh][nr + 1]): column 0 of row h = #{i : d^2 < edges2[0]}, column b + 1 =
+ *   #{i : edges2[b] <= d^2 < edges2[b + 1]}.  edges2: HOST double[nr + 1], the squares of the edges, strictly ascending from
+ *   >= 0; 1 <= nr <= 256.  The reach sqrt(edges2[nr]) must stay below L_a / 2 and within the side L_a / ncell_a of the cells
+ *   binned (the caller leaves the margin for the rounding of a cell index: pair_cells of halos.py).  Integer counts: the same
+ *   bit for bit from call to call and for any order of the particles.  *bad = 1 if a centre is not finite or has
+ *   |x| >= 2^52 L (the rows are then undefined).  Synchronises.
+ * fb_halo_apertures: per centre h the particles with d^2 < r2[h] (r2: DEVICE double[nh]): count_out (DEVICE uint32[nh]) = their
+ *   number m; com_out (DEVICE double[nh][3]) = wrap(c + sum d / m), c the wrapped centre; with vmean_out (DEVICE
+ *   double[nh][3]) and sigma_out (DEVICE double[nh]) -- both or neither, and only on a buffer binned with velocities --
+ *   vmean = sum v / m and sigma = sqrt(max(0, (sum v.v / m - vmean.vmean) / 3)), v.v = (vx vx + vy vy) + vz vz; m = 0: NaN.
+ *   The sums are fixed-point in two 64-bit words with F = 93 - e fractional bits, bound < 2^e (frexp), the bound being
+ *   n max(L) / 2 for the offsets, n max|v| for the velocities and 3 n max|v|^2 for v.v: the same bit for bit from call to
+ *   call and for any order of the particles.  reach >= every sqrt(r2[h]), under the same limits as the reach of the profiles;
+ *   *bad has bit 8 set if some r2[h] > reach^2 (or is NaN) and bit 1 for a bad centre; the outputs of such a centre are not
+ *   written.  Synchronises.                                                                                                  */
+int64_t fb_profile_work_bytes(int64_t n, int64_t ncells, int with_vel);
+int fb_profile_bin(fb_plan* plan, const double* pos, int64_t n, const double* vel, const int* ncell, void* work, int64_t work_bytes,
+                   int* bad, double* stage_ms, void* stream);
+int fb_halo_profiles(fb_plan* plan, void* work, const double* centres, int64_t nh, const double* edges2, int nr,
+                     uint32_t* counts_out, int* bad, void* stream);
+int fb_halo_apertures(fb_plan* plan, void* work, const double* centres, const double* r2, int64_t nh, double reach,
+                      uint32_t* count_out, double* com_out, double* vmean_out, double* sigma_out, int* bad, void* stream);
+
 /* ---- transfer functions (apply_transfer_fn box.py:374-379, smooth_field :651-653) ---------- */
 #define FB_FILT_TABLE 0          /* table: real multiplier, same layout as the field */
 #define FB_FILT_BEAM_HIGHPASS 1  /* (1-exp(-.5(|kpar|/p0)^p2)) [p0>0] * exp(-.5(kperp/p1)^2) [p1>0] */
