@@ -147,6 +147,8 @@ SIGNATURES = {
     "fb_gcr_finish": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_u64, c_u64, c_void_p,
                               c_void_p, c_int, c_int, c_void_p, c_void_p]),
     "fb_replace_nan_channel_mean": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fb_lssa": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, P_double, P_double, ctypes.POINTER(c_i64),
+                        c_void_p]),
     "fb_los_polyfit": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                c_void_p, c_void_p, P_i32, c_void_p]),
     "fb_los_powerlaw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_double, c_void_p, c_int,

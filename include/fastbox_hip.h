@@ -715,6 +715,28 @@ int fb_gcr_finish(fb_plan* plan, const double* sqrtS_dev, const double* x, doubl
                   int inpaint, void* cube_out, void* stream);
 int fb_replace_nan_channel_mean(fb_plan* plan, const void* cube, void* cube_out, double* mean_dev, void* stream);
 
+/* ---- least-squares spectral analysis of flagged cubes (fastbox/inpaint.py:158-399), fb_lssa.hip ----
+ * Per line of sight p and mode n, with the phase tables of the host (mode-major double[ntau][N] on the device: cos phi and
+ * sin phi; the device never derives a phase) and g = taper^2 w^2 / var (exactly 0 where w = 0):
+ *   A_re = sum_j g d cos / G_p,  A_im = -sum_j g d sin / G_p,  G_p = sum_j g   (d is selected away where g = 0: NaN is legal)
+ *   S_cc = sum_j w^2 cos^2,  S_cs = sum_j w^2 cos sin,  S_ss = sum_j w^2 - S_cc
+ *   theta = atan2(2 S_cs, S_cc - S_ss) / 2,  (A_1, A_2) = R(theta) (A_re, A_im),  l_0, l_1 = diag(R S R^T)
+ *   ps = ((A_1 l_1)^2 + (A_2 l_0)^2) / (l_0^2 + l_1^2);  without `decorrelate` ps = A_re^2 + A_im^2
+ * in one fused kernel on the fp64 matrix cores.  A row with G_p = 0 has A = 0 and ps = NaN and is left
+ * out of the averages.  All sums in a fixed order; results are bitwise repeatable.  N <= 1024, 1 <= ntau <= 1024.
+ *
+ * fb_lssa: d: cube in the plan's precision.  w: such a cube (FB_GCR_PER_VOXEL) or double[N] on the device
+ *   (FB_GCR_PER_CHANNEL); var: NULL (1), double[N] on the device (FB_GCR_PER_CHANNEL) or a cube in the plan's precision
+ *   (FB_GCR_PER_VOXEL); taper_dev: double[N] on the device or NULL (1).  With per-channel flags the overlap sums do not
+ *   depend on p and come from the host as s_dev = double[3][ntau] on the device (S_cc, S_cs, S_ss; needed with
+ *   `decorrelate`, not read with per-voxel flags).  A_re, A_im, ps: double[N^2][ntau] on the device, each may be NULL
+ *   (not stored).  With amps_given, A_re and A_im are inputs (d is not read, nor the tables with per-channel flags) and only ps and the
+ *   averages are formed.  ps_mean_out[ntau], ps_stderr_out[ntau], n_los_out (host, each may be NULL): over the n_los rows
+ *   with G_p > 0 the mean of ps and its population standard deviation / sqrt(n_los).  Synchronises.                           */
+int fb_lssa(fb_plan* plan, const void* d, const void* w, int w_kind, const void* var, int var_kind, const double* taper_dev,
+            const double* cos_dev, const double* sin_dev, const double* s_dev, int ntau, int decorrelate, int amps_given, double* A_re, double* A_im, double* ps, double* ps_mean_out,
+            double* ps_stderr_out, long long* n_los_out, void* stream);
+
 /* ---- model fits along the line of sight (fastbox/filters.py:494-593 gpr_filter, :598-664 LSQfitting), fb_losfit.hip ----
  * One wave per line of sight p (a row of the (N^2, N) view), all fit state fp64, every sum in a fixed order; N <= 1024.  w and
  * sigma: NULL (1 everywhere), double[N] on the device (FB_GCR_PER_CHANNEL) or a cube in the plan's precision

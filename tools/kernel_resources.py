@@ -29,7 +29,7 @@ def main():
             cur[k] = v
     for r in rows:
         name = subprocess.run(["c++filt", r["name"]], capture_output=True, text=True).stdout.strip()
-        name = re.sub(r"\(.*", "", name).replace("void fb::", "")
+        name = re.sub(r"\(.*", "", name.replace("(anonymous namespace)::", "")).replace("void fb::", "")
         if filters and not all(f in name for f in filters):
             continue
         print("%-62s vgpr %4s agpr %3s sgpr %4s scratch %5s occ %s spill s/v %s/%s" % (
