@@ -763,7 +763,6 @@ __device__ __forceinline__ void rsd_remap_line32(const float (&vin)[E], const fl
     };
     const double inv_Hz = 1.0 / Hz, inv_len = 1.0 / len;
     const double cells = (double)(N - 1);
-    const double s_max = __longlong_as_double(__double_as_longlong(cells) - 1);     // largest double < N - 1
     u32 kb[E];
     int cell[E];
     float nz[E];
@@ -789,8 +788,12 @@ __device__ __forceinline__ void rsd_remap_line32(const float (&vin)[E], const fl
         if (sigma_nl > 0.0) { asm volatile(""); vel = vel + sigma_nl * (double)nz[e]; }
         // reciprocals replace the two fp64 divisions (displacement, wrap); the wrap is a fract()
         const double a = fma(-vel, inv_Hz, zown(e) - len);                        // z_m - zmin - vel / H
-        double sp = __builtin_amdgcn_fract(a * inv_len) * cells;                  // in [0, N - 1]
-        sp = sp < s_max ? sp : s_max;
+        // The key is the position ROUNDED to the key's resolution (half a unit added, then truncated below): a sample within
+        // rounding of a grid point -- every sample at rest -- is an exact hit on it, as it is for np.interp, and not the last
+        // key of the cell below, which would turn the topmost occupied grid point of a line at rest into the fill value.
+        // A position that reaches the end of the line is the line's start (the periodic wrap).
+        double sp = fma(__builtin_amdgcn_fract(a * inv_len), cells, 2.3283064365386962890625e-10);     // + 2^-32, in [0, N - 1]
+        sp = sp < cells ? sp : 0.0;
         const int c = (int)sp;                                                     // 0 .. N - 2
         kb[e] = (u32)((sp - (double)c) * 2147483648.0) + 1u;                       // 1 .. 2^31
         cell[e] = sw(c);

@@ -118,6 +118,17 @@ def los_noise(N, seed, dtype=np.float64):
     return stream_normals(N ** 3, 1, seed, 0, dtype).reshape(N, N, N)
 
 
+def los_noise_lines(N, seed, lines, dtype=np.float64):
+    """Rows `lines` (flat line-of-sight numbers i N + j) of los_noise(N, seed).reshape(N * N, N), without the N^3 array:
+    element los N + m is output (los N + m) & 3 of call (los N + m) >> 2 of stream 1.  Returns (len(lines), N)."""
+    los = np.asarray(lines, dtype=np.uint64).reshape(-1, 1)
+    idx = los * np.uint64(N) + np.arange(N, dtype=np.uint64)[None, :]
+    o = _call(idx >> np.uint64(2), 1, seed, 0)
+    g = box_muller(o[0], o[1], dtype) + box_muller(o[2], o[3], dtype)
+    w = (idx & np.uint64(3)).astype(np.int64)
+    return np.where(w == 0, g[0], np.where(w == 1, g[1], np.where(w == 2, g[2], g[3])))
+
+
 def sky_map_noise(N, seed, dtype=np.float64):
     """(re, im), each (N, N), of the foreground amplitude map (k_sky_colour_map, stream 2): element q = x N + y takes
     normals 2 q and 2 q + 1 of the stream -- call q >> 1, words (0, 1) for even q and (2, 3) for odd q.  `seed`:
