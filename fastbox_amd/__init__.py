@@ -16,6 +16,9 @@ from . import inpaint                             # noqa: F401
 from . import losfit                              # noqa: F401
 from .losfit import GPRKernel, LSQfitting         # noqa: F401
 from . import analysis                            # noqa: F401
+from .analysis import interpolate_onto_grid, grid_catalogue   # noqa: F401
+from . import utils                               # noqa: F401
+from .utils import comoving_dimensions_from_survey            # noqa: F401
 from . import montecarlo                          # noqa: F401
 from .beams import BeamModel                      # noqa: F401
 from .halos import HaloDistribution, HaloCatalogue, ColaParticles   # noqa: F401

@@ -154,6 +154,11 @@ SIGNATURES = {
     "fb_los_powerlaw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_double, c_void_p, c_int,
                                 c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, P_i32, c_void_p]),
     "fb_los_subtract": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fb_regrid_trilinear": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int,
+                                    c_void_p, c_int, c_void_p, c_int, c_int, c_void_p, c_void_p]),
+    "fb_grid_catalogue": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                  c_void_p, c_void_p]),
+    "fb_position_range": (c_int, [c_void_p, c_void_p, c_i64, P_double, c_void_p]),
     "fb_sky_realise_map": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_double, c_void_p, c_void_p, c_void_p]),
     "fb_sky_normal_map": (c_int, [c_void_p, c_void_p, c_u64, c_double, c_double, c_void_p, c_void_p]),
     "fb_sky_gaussian_filter": (c_int, [c_void_p, c_void_p, c_void_p, P_double, c_int, c_void_p]),

@@ -188,6 +188,15 @@ def comoving_angular_distance(cosmo, a):
                  * _TRAPZ(1.0 / (aa * aa * _E(cosmo, aa)), aa))
 
 
+def comoving_radial_distance(cosmo, a):
+    """Comoving radial distance to scale factor ``a`` in Mpc; ``a`` a number or an array, as pyccl takes it.  The models
+    carried here are flat, where it equals ``comoving_angular_distance``."""
+    if np.ndim(a) == 0:
+        return comoving_angular_distance(cosmo, a)
+    aa = np.asarray(a, dtype=np.float64)
+    return np.array([comoving_angular_distance(cosmo, v) for v in aa.ravel()]).reshape(aa.shape)
+
+
 def linear_matter_power(cosmo, k, a):
     """P_lin(k, a) in Mpc^3 for ``k`` in 1/Mpc; NaN at k = 0 (the reference
     relies on ``nan_to_num`` to zero the DC mode, fastbox/box.py:167)."""

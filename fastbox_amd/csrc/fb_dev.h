@@ -133,6 +133,34 @@ __device__ __forceinline__ double fx_join(unsigned long long hi, unsigned long l
     return ldexp((double)(long long)hi * 4294967296.0 + (double)lo, -F);
 }
 
+// The kernels every fixed-point mesh shares (fb_paint, fb_grid_catalogue): the bound sum |w| (n for no weights) in per-workgroup
+// partials, the one-workgroup finish of such partials in a fixed order (op 0: sum, 1: max, an empty max being 0), and the
+// conversion of the accumulators to the plan's reals.  F = 61 - e with sum |w| < 2^e, so no node can overflow 62 bits; TWO
+// (fp64 plans): 32 more bits, split over two accumulators.  Templates for the reason k_bin_finish is one.
+template <int = 0>
+static __global__ __launch_bounds__(256) void k_paint_wsum(const double* w, unsigned long long n, double* partials) {
+    double acc = 0.0;
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256)
+        acc += w ? fabs(w[i]) : 1.0;
+    acc = block_reduce(acc, 0);
+    if (threadIdx.x == 0) partials[blockIdx.x] = acc;
+}
+template <int = 0>
+static __global__ __launch_bounds__(256) void k_halo_finish(const double* partials, int nb, int op, double* out) {
+    double acc = op ? -INFINITY : 0.0;
+    for (int i = threadIdx.x; i < nb; i += 256) acc = op ? fmax(acc, partials[i]) : acc + partials[i];
+    acc = block_reduce(acc, op);
+    if (threadIdx.x == 0) out[0] = op && !(acc > -INFINITY) ? 0.0 : acc;
+}
+template <typename T, bool TWO>
+static __global__ __launch_bounds__(256) void k_paint_finish(const unsigned long long* acc_hi, const unsigned long long* acc_lo,
+                                                             unsigned long long n, const double* wsum, T* out) {
+    const int F = fx_exponent(wsum[0], 61) + (TWO ? 32 : 0);
+    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
+        out[i] = (T)(TWO ? fx_join(acc_hi[i], acc_lo[i], F) : ldexp((double)(long long)acc_hi[i], -F));
+    }
+}
+
 // ---- host -------------------------------------------------------------------------------------------------------------------
 // workgroups of 256 lanes for a grid-stride loop over n elements: one per 256 elements, at most 64 per compute unit
 inline int grid_for(unsigned long long n, const fb_plan* p) {

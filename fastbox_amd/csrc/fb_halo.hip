@@ -48,13 +48,7 @@ __global__ __launch_bounds__(256) void k_halo_ln_reduce(const T* dx, HPrm bias, 
     acc = block_reduce(acc, op);
     if (threadIdx.x == 0) partials[blockIdx.x] = acc;
 }
-// one workgroup: out[0] = reduction of partials[0..nb) in a fixed order
-__global__ __launch_bounds__(256) void k_halo_finish(const double* partials, int nb, int op, double* out) {
-    double acc = op ? -INFINITY : 0.0;
-    for (int i = threadIdx.x; i < nb; i += 256) acc = op ? fmax(acc, partials[i]) : acc + partials[i];
-    acc = block_reduce(acc, op);
-    if (threadIdx.x == 0) out[0] = op && !(acc > -INFINITY) ? 0.0 : acc;
-}
+// (k_halo_finish<> of fb_dev.h: one workgroup, out[0] = reduction of partials[0..nb) in a fixed order)
 
 // Poisson variate by inversion of the CDF with one uniform u in (0, 1), in fp64.  The search starts at the mode
 // m = floor(lam) with pmf exp(m ln lam - lam - lgamma(m + 1)); the mass below the mode is summed downwards until a term falls
@@ -240,14 +234,7 @@ __global__ __launch_bounds__(256) void k_cat_emit(const T* counts, unsigned long
 // Fixed point: every contribution x = w W is added as the integer round(x 2^F) -- order-independent, so the mesh is the same
 // bit for bit from call to call.  F = 61 - e with sum |w| < 2^e, so no node can overflow 62 bits.  TWO (fp64 plans): v = x 2^F'
 // with F' = F + 32 is split into hi = floor(v 2^-32) (int64) and lo = v - hi 2^32 in [0, 2^32], two accumulators: about 94
-// significant bits per node.
-__global__ __launch_bounds__(256) void k_paint_wsum(const double* w, unsigned long long n, double* partials) {
-    double acc = 0.0;
-    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256)
-        acc += w ? fabs(w[i]) : 1.0;
-    acc = block_reduce(acc, 0);
-    if (threadIdx.x == 0) partials[blockIdx.x] = acc;
-}
+// significant bits per node.  k_paint_wsum<> and k_paint_finish<> live in fb_dev.h: fb_regrid.hip's histogram shares them.
 // nodes and weights of one axis: window 0 ngp, 1 cic, 2 tsc
 __device__ __forceinline__ int axis_weights(double u, int window, int N, long long (&m)[3], double (&w)[3]) {
     if (window == 1) {
@@ -296,15 +283,6 @@ __global__ __launch_bounds__(256) void k_paint(const double* pos, const double* 
             }
     }
 }
-template <typename T, bool TWO>
-__global__ __launch_bounds__(256) void k_paint_finish(const unsigned long long* acc_hi, const unsigned long long* acc_lo,
-                                                      unsigned long long n, const double* wsum, T* out) {
-    const int F = fx_exponent(wsum[0], 61) + (TWO ? 32 : 0);
-    for (unsigned long long i = (unsigned long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (unsigned long long)gridDim.x * 256) {
-        out[i] = (T)(TWO ? fx_join(acc_hi[i], acc_lo[i], F) : ldexp((double)(long long)acc_hi[i], -F));
-    }
-}
-
 // compensation: every stored mode of a half spectrum divided by prod_a sinc(pi m_a / N)^p, then the c2r's 1/N^3
 template <typename T>
 __global__ __launch_bounds__(256) void k_paint_compensate(T* half, int N, int NR, int NZP, int p) {
@@ -357,14 +335,14 @@ int halo_lambda(fb_plan* p, const void* delta, HPrm nbar, HPrm bias, double vv, 
         if (sizeof(T) == 4) {          // shift by the maximum (single-precision plans; fp64 plans follow the reference: no shift)
             hipLaunchKernelGGL((k_halo_ln_reduce<T>), dim3(nb), dim3(256), 0, s, (const T*)delta, bias, n, p->N, 1, stats, part);
             FB_LAUNCH_CHECK("k_halo_ln_reduce");
-            hipLaunchKernelGGL(k_halo_finish, dim3(1), dim3(256), 0, s, part, nb, 1, stats);
+            hipLaunchKernelGGL(k_halo_finish<>, dim3(1), dim3(256), 0, s, part, nb, 1, stats);
             FB_LAUNCH_CHECK("k_halo_finish");
         } else {
             FB_HIP(hipMemsetAsync(stats, 0, sizeof(double), s));
         }
         hipLaunchKernelGGL((k_halo_ln_reduce<T>), dim3(nb), dim3(256), 0, s, (const T*)delta, bias, n, p->N, 0, stats, part);
         FB_LAUNCH_CHECK("k_halo_ln_reduce");
-        hipLaunchKernelGGL(k_halo_finish, dim3(1), dim3(256), 0, s, part, nb, 0, stats + 1);
+        hipLaunchKernelGGL(k_halo_finish<>, dim3(1), dim3(256), 0, s, part, nb, 0, stats + 1);
         FB_LAUNCH_CHECK("k_halo_finish");
     }
     { FbProfScope _ps(p, FBK_REALOP, s);
@@ -437,9 +415,9 @@ int paint(fb_plan* p, const double* pos, const double* wt, unsigned long long n,
     unsigned long long* lo = TWO ? hi + nv : nullptr;
     FB_HIP(hipMemsetAsync(hi, 0, nv * 8 * (TWO ? 2 : 1), s));
     const int nb = std::min(grid_for(n, p), FB_HALO_RED_BLOCKS);
-    hipLaunchKernelGGL(k_paint_wsum, dim3(nb), dim3(256), 0, s, wt, n, part);
+    hipLaunchKernelGGL(k_paint_wsum<>, dim3(nb), dim3(256), 0, s, wt, n, part);
     FB_LAUNCH_CHECK("k_paint_wsum");
-    hipLaunchKernelGGL(k_halo_finish, dim3(1), dim3(256), 0, s, (const double*)part, nb, 0, wsum);
+    hipLaunchKernelGGL(k_halo_finish<>, dim3(1), dim3(256), 0, s, (const double*)part, nb, 0, wsum);
     FB_LAUNCH_CHECK("k_halo_finish");
     if (n) {
         FbProfScope _ps(p, FBK_REALOP, s);

@@ -780,6 +780,38 @@ int fb_los_powerlaw(fb_plan* plan, const void* maps, const double* tpsmean_dev, 
                     int32_t* n_failed_out, void* stream);
 int fb_los_subtract(fb_plan* plan, const void* X, const double* Y, const double* shift_dev, void* cube_out, void* stream);
 
+/* ---- putting data onto a grid (fastbox/analysis.py:31-70 interpolate_onto_grid, :73-118 grid_catalogue), fb_regrid.hip ----
+ * fb_regrid_trilinear: cube T[nx][ny][nz] (plan precision, every axis >= 2) given at the nodes gx[nx], gy[ny], gz[nz], each
+ *   strictly ascending (the caller's check; any table is memory-safe), interpolated at the points px[npx], py[npy], pz[npz]
+ *   (any order, each >= 1 long): scipy's RegularGridInterpolator(method='linear', bounds_error=False, fill_value=nan) behind
+ *   replace_nan_with_channel_mean.  All six tables are DEVICE double; all coordinate and weight arithmetic is fp64.  Per axis:
+ *     i = clip(searchsorted(g, p, 'right') - 1, 0, n - 2),  t = (p - g[i]) / (g[i + 1] - g[i]),
+ *     p is inside iff g[0] <= p <= g[n - 1] (both ends closed; NaN is outside);
+ *   value = sum over the eight corners, x outermost and z innermost, of v ((w_x w_y) w_z) with w = 1 - t at node i and t at
+ *   node i + 1, starting from 0; zero weights are not skipped, so a NaN corner of weight 0 gives NaN.  A point outside on any
+ *   axis gives NaN.  A NaN voxel of the cube reads as the mean of its channel (last axis) over the nx ny voxels that are not NaN,
+ *   summed in fp64 in a fixed order (bitwise repeatable); no filled copy is written; a channel that is NaN throughout stays NaN.
+ *   out: T[npx][npy][npz] or, with swap_xy, T[npy][npx][npz] -- element [j][i][k] at (px[i], py[j], pz[k]), the order of
+ *   numpy's default 'xy' meshgrid that the reference returns.  Indexing is 64-bit.  Work memory: the plan's shared work buffer
+ *   (npx + npy + npz cells and fractions, up to 512 nz partial sums).  Asynchronous.
+ * fb_grid_catalogue: out T[nx][ny][nz] = np.histogramdd(pos, bins=(nx, ny, nz), range=..., weights=weights) for the edge tables
+ *   edges_x[nx + 1], edges_y[ny + 1], edges_z[nz + 1] (DEVICE double, non-decreasing: the caller's np.linspace(lo, hi, n + 1), so
+ *   that the device compares with the same doubles as numpy).  pos: DEVICE double[n][3]; weights: DEVICE double[n] or NULL
+ *   (all 1).  Bin = searchsorted(edges, p, 'right') - 1, a point equal to the last edge in the last bin; a point outside
+ *   [edges[0], edges[n]] or NaN on any axis is dropped.  Not periodic.  Accumulated in fb_paint's fixed point (int64 with
+ *   F = 61 - e, sum |w| < 2^e over all n particles; two words and 32 more bits on fp64 plans): the same bit for bit from call
+ *   to call and for any particle order; unweighted counts are exact integers up to what T holds (2^24 per cell on a
+ *   single-precision plan, 2^53 on fp64), at most 2^31 particles per cell.  The accumulators (8 or 16 bytes per cell) are
+ *   plan-owned: FB_ERR_NOMEM if they do not fit.  Asynchronous.
+ * fb_position_range: lohi6 (HOST) = {min x, max x, min y, max y, min z, max z} of pos (DEVICE double[n][3], n >= 1); both
+ *   values of an axis are NaN if one of its coordinates is (numpy's min / max), infinities as they come.  Synchronises.     */
+int fb_regrid_trilinear(fb_plan* plan, const void* cube, int nx, int ny, int nz, const double* gx, const double* gy,
+                        const double* gz, const double* px, int npx, const double* py, int npy, const double* pz, int npz,
+                        int swap_xy, void* out, void* stream);
+int fb_grid_catalogue(fb_plan* plan, const double* pos, const double* weights, int64_t n, const double* edges_x, int nx,
+                      const double* edges_y, int ny, const double* edges_z, int nz, void* out, void* stream);
+int fb_position_range(fb_plan* plan, const double* pos, int64_t n, double* lohi6, void* stream);
+
 /* ---- the steps after the density-field path: foregrounds (fastbox/foregrounds.py:48-175) and radiometer
  * noise (fastbox/noise.py:25-75).  2-D maps are T[N][N] over (x, y); cubes T[N][N][N], frequency axis last. ---- */
 /* realise_foreground_amp (:99-107): map_out = Re ifft2((re + i im) amp2d) + monopole.  amp2d = sqrt(C_ell) per
