@@ -22,5 +22,7 @@ from .utils import comoving_dimensions_from_survey            # noqa: F401
 from . import montecarlo                          # noqa: F401
 from .beams import BeamModel                      # noqa: F401
 from .halos import HaloDistribution, HaloCatalogue, ColaParticles   # noqa: F401
+from . import recon                               # noqa: F401
+from .recon import Reconstruction                 # noqa: F401
 
 __version__ = "0.1.0"

@@ -159,6 +159,12 @@ SIGNATURES = {
     "fb_grid_catalogue": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
                                   c_void_p, c_void_p]),
     "fb_position_range": (c_int, [c_void_p, c_void_p, c_i64, P_double, c_void_p]),
+    "fb_recon_work_bytes": (c_i64, [c_void_p, c_i64, c_i64]),
+    "fb_recon_displacement": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_void_p]),
+    "fb_mesh_readout": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_i64, c_int, c_void_p, c_void_p]),
+    "fb_recon_shift": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_double, c_double, c_void_p, c_void_p]),
+    "fb_uniform_positions": (c_int, [c_void_p, c_u64, c_u64, c_i64, c_void_p, c_void_p]),
+    "fb_grid_positions": (c_int, [c_void_p, c_void_p, c_void_p]),
     "fb_sky_realise_map": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_double, c_void_p, c_void_p, c_void_p]),
     "fb_sky_normal_map": (c_int, [c_void_p, c_void_p, c_u64, c_double, c_double, c_void_p, c_void_p]),
     "fb_sky_gaussian_filter": (c_int, [c_void_p, c_void_p, c_void_p, P_double, c_int, c_void_p]),

@@ -1194,6 +1194,44 @@ class CosmoBox(object):
         from . import halos
         return halos.spherical_overdensity(self, centres, particles, **kw)
 
+    # ------------------------------------------------------------ density-field reconstruction and mesh readout
+    def reconstruct(self, data, randoms=None, smoothing=10., bias=1., f=0., convention='sym', window='cic', delta=None,
+                    seed=None, return_displacement=False):
+        """Additive: density-field (BAO) reconstruction on the device -- what pyrecon's and nbodykit's FFT reconstruction give
+        the host pipelines (Eisenstein et al. 2007; Padmanabhan et al. 2012; Burden et al. 2014); definition in DESIGN.md
+        section 4.  delta = n / nbar - 1 of ``data`` painted with ``window`` (or the real mesh ``delta``, used as it is: a
+        cleaned intensity map, say); Psi_a(k) = i k_a delta(k) exp(-k^2 R^2 / 2) / (b (k^2 + beta k_z^2)) with R = ``smoothing``
+        (Mpc), b = ``bias``, beta = f / b, the line of sight along z; the data move to wrap(x - Psi(x) - f Psi_z(x) z^), the
+        randoms likewise with ``convention='sym'`` (RecSym) and by -Psi alone with ``'iso'`` (RecIso); ``delta_rec`` =
+        D / nbar_D - S / nbar_S of the two shifted sets painted with the same window.  ``data``: ColaParticles, FoFHalos,
+        SOHalos or another HaloCatalogue of this box, or a host (n, 3) array (Mpc, periodic, wrapped on read).  ``randoms``:
+        None: 4 n uniform points drawn on the device (Philox stream 10 with ``seed``, default the box's: the same points on
+        every call); an integer: that many; 'grid': one on each mesh node, no shot noise; or a catalogue / (n, 3) array.
+        Returns a ``fastbox_amd.recon.Reconstruction`` (delta_rec, the shifted data and randoms as HaloCatalogues, the
+        displacement with ``return_displacement``).  ValueError / TypeError name the argument: positions that are not finite
+        or have |x| >= 2^52 L, more than 2^31 - 2 particles, smoothing <= 0, bias <= 0, f < 0, an unknown convention or
+        window, a complex ``delta``; MemoryError before any kernel runs if the work memory does not fit.  Agreement with
+        pyrecon and nbodykit is intended, not verified."""
+        from . import recon
+        return recon.reconstruct(self, data, randoms=randoms, smoothing=smoothing, bias=bias, f=f, convention=convention,
+                                 window=window, delta=delta, seed=seed, return_displacement=return_displacement)
+
+    def readout(self, field, positions, window='cic'):
+        """Additive: mesh -> particle interpolation, the adjoint of ``paint_catalogue``: the value of a real field of this
+        box at each position through the window's nodes and weights ('ngp', 'cic', 'tsc'; fp64 weights on both precisions).
+        ``field``: a real DeviceArray or host (N, N, N) array, or a list of up to three (a velocity, a displacement);
+        ``positions``: a HaloCatalogue of this box or a host (n, 3) array, periodic.  Returns fp64 values on the device,
+        shape (n,) or, for a list, (n, k); ``np.asarray`` copies them to the host."""
+        from . import recon
+        return recon.readout(self, field, positions, window=window)
+
+    def uniform_catalogue(self, n, seed=None):
+        """Additive: ``n`` points uniform in the box, drawn on the device (Philox stream 10; ``seed`` default the box's; every
+        call without a seed of its own takes the box's next draw), as a HaloCatalogue.  Host model:
+        ``fastbox_amd.rng.recon_uniforms(n, L, seed, realisation)`` with the catalogue's ``seed`` and ``realisation``."""
+        from . import recon
+        return recon.uniform_catalogue(self, n, seed=seed)
+
     def sigmaR(self, R):
         """RMS of the field smoothed with a top-hat of R Mpc/h, from the binned power
         spectrum (box.py:657-683; scipy's simps is spelled simpson since 1.14)."""

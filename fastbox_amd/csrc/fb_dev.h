@@ -24,6 +24,24 @@ __device__ __forceinline__ double wrap_pos(double x, double L) {
     if (x >= L) x -= L;
     return x;
 }
+// nodes and weights of one axis of the mass-assignment windows, at u = x N / L cells: window 0 ngp, 1 cic, 2 tsc (fb_paint's
+// header comment in include/fastbox_hip.h).  Returns the number of nodes.  Painting (fb_halo.hip) and reading the mesh back
+// (fb_recon.hip) share it, so that the two are adjoint to the bit.
+__device__ __forceinline__ int axis_weights(double u, int window, int N, long long (&m)[3], double (&w)[3]) {
+#pragma clang fp contract(off)
+    if (window == 1) {
+        const double f0 = floor(u), f = u - f0;
+        m[0] = wrap_node((long long)f0, N); m[1] = wrap_node((long long)f0 + 1, N);
+        w[0] = 1.0 - f; w[1] = f;
+        return 2;
+    }
+    const double c = floor(u + 0.5);
+    if (window == 0) { m[0] = wrap_node((long long)c, N); w[0] = 1.0; return 1; }
+    const double d = u - c, a = 0.5 - d, b = 0.5 + d;
+    m[0] = wrap_node((long long)c - 1, N); m[1] = wrap_node((long long)c, N); m[2] = wrap_node((long long)c + 1, N);
+    w[0] = 0.5 * (a * a); w[1] = 0.75 - d * d; w[2] = 0.5 * (b * b);
+    return 3;
+}
 
 // ---- wave reductions: over the 64 lanes, the result in every lane -----------------------------------------------------------
 // float: six DPP adds (row_shr 1, 2, 4, 8, then row_bcast 15 and 31 carry the row totals forward; lanes a step does not

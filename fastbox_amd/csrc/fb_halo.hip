@@ -235,21 +235,7 @@ __global__ __launch_bounds__(256) void k_cat_emit(const T* counts, unsigned long
 // bit for bit from call to call.  F = 61 - e with sum |w| < 2^e, so no node can overflow 62 bits.  TWO (fp64 plans): v = x 2^F'
 // with F' = F + 32 is split into hi = floor(v 2^-32) (int64) and lo = v - hi 2^32 in [0, 2^32], two accumulators: about 94
 // significant bits per node.  k_paint_wsum<> and k_paint_finish<> live in fb_dev.h: fb_regrid.hip's histogram shares them.
-// nodes and weights of one axis: window 0 ngp, 1 cic, 2 tsc
-__device__ __forceinline__ int axis_weights(double u, int window, int N, long long (&m)[3], double (&w)[3]) {
-    if (window == 1) {
-        const double f0 = floor(u), f = u - f0;
-        m[0] = wrap_node((long long)f0, N); m[1] = wrap_node((long long)f0 + 1, N);
-        w[0] = 1.0 - f; w[1] = f;
-        return 2;
-    }
-    const double c = floor(u + 0.5);
-    if (window == 0) { m[0] = wrap_node((long long)c, N); w[0] = 1.0; return 1; }
-    const double d = u - c, a = 0.5 - d, b = 0.5 + d;
-    m[0] = wrap_node((long long)c - 1, N); m[1] = wrap_node((long long)c, N); m[2] = wrap_node((long long)c + 1, N);
-    w[0] = 0.5 * (a * a); w[1] = 0.75 - d * d; w[2] = 0.5 * (b * b);
-    return 3;
-}
+// (axis_weights, the nodes and weights of one axis, lives in fb_dev.h: fb_recon.hip reads the mesh back through them)
 template <bool TWO>
 __global__ __launch_bounds__(256) void k_paint(const double* pos, const double* wt, unsigned long long n, int window, int N,
                                                double s0, double s1, double s2, const double* wsum,

@@ -226,3 +226,22 @@ def scatter_uniforms(nh, seed, realisation=0):
     """(nh, 3) offsets of the device-scattered catalogue: (1 - 1e-8) (o_a 2^-32), words 0-2 of Philox call h, stream 6."""
     o = _call(np.arange(nh, dtype=np.uint64), 6, seed, realisation)
     return np.stack([(1. - 1e-8) * (o[a].astype(np.float64) * 2.3283064365386963e-10) for a in range(3)], axis=-1)
+
+
+# ---- reconstruction randoms (fb_recon.hip): uniform positions on stream 10 ------------------------------------------------------
+def recon_uniforms(n, L, seed, realisation=0, first=0):
+    """(n, 3) positions of fb_uniform_positions, bit for bit: point p takes Philox calls 2 p and 2 p + 1 of stream 10 (one call
+    holds 128 bits, three 53-bit uniforms need 159) -- x from words (0, 1) and y from words (2, 3) of call 2 p, z from words
+    (0, 1) of call 2 p + 1; u = (w + 1/2) 2^-53 with w = (a << 21) | (b >> 11), as poisson_uniforms; the coordinate is
+    min(u L_a, the largest double below L_a): w + 1/2 rounds to 2^53 for the last w, so u = 1 occurs.  ``L``: (Lx, Ly, Lz);
+    ``first``: the first point."""
+    p = np.arange(first, first + n, dtype=np.uint64)
+    o = _call(np.uint64(2) * p, 10, seed, realisation)
+    q = _call(np.uint64(2) * p + np.uint64(1), 10, seed, realisation)
+
+    def u53(a, b):
+        w = (a << np.uint64(21)) | (b >> np.uint64(11))
+        return (w.astype(np.float64) + 0.5) * 1.1102230246251565e-16
+
+    u = (u53(o[0], o[1]), u53(o[2], o[3]), u53(q[0], q[1]))
+    return np.stack([np.minimum(u[a] * float(L[a]), np.nextafter(float(L[a]), 0.)) for a in range(3)], axis=-1)

@@ -812,6 +812,45 @@ int fb_grid_catalogue(fb_plan* plan, const double* pos, const double* weights, i
                       const double* edges_y, int ny, const double* edges_z, int nz, void* out, void* stream);
 int fb_position_range(fb_plan* plan, const double* pos, int64_t n, double* lohi6, void* stream);
 
+/* ---- density-field (BAO) reconstruction and mesh readout (definition in DESIGN.md section 4; numpy statement in
+ * tests/recon_numpy.py) ---------------------------------------------------------------------------------------------------
+ * One box on one GPU, any box shape (Lx, Ly, Lz), both precisions, every grid the FFT takes.  Particle data are fp64 whatever
+ * the plan's precision: pos DEVICE double[n][3] in Mpc, 0 <= n <= 2^31 - 2.  All arithmetic is fp64; fields are read and
+ * written in the plan's precision.  The line of sight is z.  Everything here is asynchronous.
+ * fb_recon_displacement: psi3_out T[3][N^3] = c2r(Psi_a(k)), a = x, y, z, with
+ *     Psi_a(k) = i k_a delta(k) exp(-k^2 R^2 / 2) / (b (k^2 + beta k_z^2)),   k_a = 2 pi m_a / L_a, m_a the signed FFT index,
+ *   the plane-parallel solution of div Psi + beta d_z Psi_z = -delta_smoothed / b for an irrotational Psi (beta = f / b;
+ *   beta = 0: the Zel'dovich displacement of delta / b).  Zero at k = 0; component a is zero on the plane m_a = -N/2 (the
+ *   convention of fb_cola_lpt; the stored k_z = N/2 plane of a half spectrum is that plane).  half_in: delta(k), a half
+ *   spectrum (fb_fft_r2c), read once and kept; half_work3: scratch of three half spectra; the c2r scale is 1 / N^3.
+ *   R > 0 (Mpc), b > 0, beta >= 0.
+ * fb_mesh_readout: out DEVICE double[n][nfields] = sum over the window's nodes of w F_c at each position, for nfields (1..3)
+ *   real fields T[nfields][N^3]; window, nodes and weights exactly fb_paint's (the readout is the adjoint of the paint), the
+ *   weight of a node ((w_x w_y) w_z), nodes summed with x outermost.  Positions are periodic: the nodes wrap, whatever the
+ *   position holds (|x| < 2^52 L); a position that is not finite reads NaN.  No atomics: bitwise repeatable.
+ * fb_recon_shift: pos_out = wrap(x - scale Psi(x) - scale_z Psi_z(x) z^), Psi(x) the readout of psi3 T[3][N^3] at x:
+ *   per axis wrap(x_a - scale Psi_a), along z wrap(x_z - (scale Psi_z + scale_z Psi_z)); wrap(x) = x - L floor(x / L), then
+ *   + L if negative and - L if >= L.  pos_out may be pos_in.  A position that is not finite gives NaN on all three axes.
+ *   For n >= N^3 / 8 the three fields are first copied interleaved (x, y, z, pad per node) into the plan's shared work buffer
+ *   (4 N^3 reals) and gathered from there, one load per node: the same sums, the same bits.
+ * fb_uniform_positions: n points uniform in the box from Philox stream 10.  Point p takes calls 2 p and 2 p + 1 of the stream
+ *   (one call holds 128 bits, three 53-bit uniforms need 159): x from words (0, 1) and y from words (2, 3) of call 2 p, z from
+ *   words (0, 1) of call 2 p + 1; u = (w + 1/2) 2^-53 with w = (a << 21) | (b >> 11); the coordinate is min(u L_a, the largest
+ *   double below L_a).  Host model: fastbox_amd/rng.py recon_uniforms, bit for bit.
+ * fb_grid_positions: pos_out DEVICE double[N^3][3] = one particle on each mesh node in C order, node m at m L_a / N (the
+ *   randoms without shot noise); N^3 <= 2^31 - 2.
+ * fb_recon_work_bytes: the device bytes CosmoBox.reconstruct allocates beside its inputs for n_data and n_random particles
+ *   (eleven real fields, four half spectra, the shifted catalogues and fb_paint's accumulators); -1: bad arguments.         */
+int64_t fb_recon_work_bytes(const fb_plan* plan, int64_t n_data, int64_t n_random);
+int fb_recon_displacement(fb_plan* plan, const void* half_in, void* half_work3, void* psi3_out, double R, double b, double beta,
+                          void* stream);
+int fb_mesh_readout(fb_plan* plan, const void* fields, int nfields, const double* pos, int64_t n, int window, double* out,
+                    void* stream);
+int fb_recon_shift(fb_plan* plan, const void* psi3, const double* pos_in, int64_t n, int window, double scale, double scale_z,
+                   double* pos_out, void* stream);
+int fb_uniform_positions(fb_plan* plan, uint64_t seed, uint64_t realisation, int64_t n, double* pos_out, void* stream);
+int fb_grid_positions(fb_plan* plan, double* pos_out, void* stream);
+
 /* ---- the steps after the density-field path: foregrounds (fastbox/foregrounds.py:48-175) and radiometer
  * noise (fastbox/noise.py:25-75).  2-D maps are T[N][N] over (x, y); cubes T[N][N][N], frequency axis last. ---- */
 /* realise_foreground_amp (:99-107): map_out = Re ifft2((re + i im) amp2d) + monopole.  amp2d = sqrt(C_ell) per
