@@ -24,5 +24,7 @@ from .beams import BeamModel                      # noqa: F401
 from .halos import HaloDistribution, HaloCatalogue, ColaParticles   # noqa: F401
 from . import recon                               # noqa: F401
 from .recon import Reconstruction                 # noqa: F401
+from . import minkowski                           # noqa: F401
+from .minkowski import MinkowskiFunctionals, minkowski_functionals   # noqa: F401
 
 __version__ = "0.1.0"

@@ -165,6 +165,9 @@ SIGNATURES = {
     "fb_recon_shift": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_int, c_double, c_double, c_void_p, c_void_p]),
     "fb_uniform_positions": (c_int, [c_void_p, c_u64, c_u64, c_i64, c_void_p, c_void_p]),
     "fb_grid_positions": (c_int, [c_void_p, c_void_p, c_void_p]),
+    "fb_minkowski_counts": (c_int, [c_void_p, c_void_p, P_double, c_int, c_int, ctypes.POINTER(c_u64), ctypes.POINTER(c_u64),
+                                    c_void_p]),
+    "fb_channel_moments": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fb_sky_realise_map": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_double, c_void_p, c_void_p, c_void_p]),
     "fb_sky_normal_map": (c_int, [c_void_p, c_void_p, c_u64, c_double, c_double, c_void_p, c_void_p]),
     "fb_sky_gaussian_filter": (c_int, [c_void_p, c_void_p, c_void_p, P_double, c_int, c_void_p]),

@@ -1232,6 +1232,22 @@ class CosmoBox(object):
         from . import recon
         return recon.uniform_catalogue(self, n, seed=seed)
 
+    # ------------------------------------------------------------ Minkowski functionals of excursion sets
+    def minkowski_functionals(self, delta_x=None, **kw):
+        """Additive: the Minkowski functionals of the excursion sets {delta_x >= t} -- volume fraction, surface, integrated
+        mean curvature and Euler characteristic (genus) densities of the periodic box, or with ``per_channel=True`` the area,
+        perimeter and Euler characteristic of every frequency channel -- from exact integer counts of the cell complex made
+        in one pass on the device.  ``delta_x`` (default ``self.delta_x``): a real DeviceArray of this box or a host (N, N, N)
+        real array; a complex field or a spectrum raises TypeError, another shape or box ValueError.  Keywords
+        (``thresholds`` | ``nu``, ``per_channel``) and definition: ``fastbox_amd.minkowski.minkowski_functionals``; DESIGN.md
+        section 4.  Returns a ``MinkowskiFunctionals``.  The box's state is left as it was."""
+        from . import minkowski
+        if delta_x is None:
+            delta_x = getattr(self, "delta_x", None)
+            if delta_x is None:
+                raise ValueError("no delta_x: realise_density() first, or pass delta_x")
+        return minkowski.minkowski_functionals(delta_x, box=self, **kw)
+
     def sigmaR(self, R):
         """RMS of the field smoothed with a top-hat of R Mpc/h, from the binned power
         spectrum (box.py:657-683; scipy's simps is spelled simpson since 1.14)."""

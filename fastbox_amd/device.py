@@ -202,6 +202,7 @@ class Engine(object):
             raise ValueError("precision must be 'f32' or 'f64'")
         self.lib = _lib.load()
         self.N = int(N)
+        self.L = (float(L[0]), float(L[1]), float(L[2]))
         self.precision = precision
         self.device = int(device)
         self.rdtype = np.float32 if precision == "f32" else np.float64

@@ -851,6 +851,25 @@ int fb_recon_shift(fb_plan* plan, const void* psi3, const double* pos_in, int64_
 int fb_uniform_positions(fb_plan* plan, uint64_t seed, uint64_t realisation, int64_t n, double* pos_out, void* stream);
 int fb_grid_positions(fb_plan* plan, double* pos_out, void* stream);
 
+/* ---- Minkowski functionals of excursion sets (fb_minkowski.hip; definition: DESIGN.md section 4, numpy statement:
+ * tests/minkowski_numpy.py).  real: T[N][N][N], periodic.  A voxel is a closed cell; an element of the cell complex (cell, face,
+ * edge, vertex) lies in the excursion set of threshold t iff the maximum of its adjacent voxels (1, 2, 4, 8 of them) is >= t,
+ * compared in fp64 on the stored value.  A NaN is below every threshold and is counted in n_nan_out; +inf is above every one.
+ * thresholds: HOST double, 1 <= nt <= 256, finite and strictly ascending (per row), else FB_ERR_INVALID before any launch.
+ *   mode 0: the box.  thresholds[nt]; counts_out HOST uint64 [8][nt] in the order n3, n2x, n2y, n2z, n1x, n1y, n1z, n0 (a face
+ *     is named by its normal, an edge by the axis it runs along); n_nan_out HOST uint64 [1].
+ *   mode 1: every channel z as a periodic 2-D map.  thresholds[nt]; counts_out [4][N][nt] in the order n2 (pixels), n1x, n1y
+ *     (edges along x, y: 2 pixels each), n0 (vertices: 4 pixels); n_nan_out [N].
+ *   mode 2: as mode 1 with thresholds[N][nt], a row per channel.
+ * One pass over the cube; integer accumulation only (32-bit per workgroup in LDS, 64-bit device totals), so the counts are
+ * exact and the same on every call.  Work memory: the thresholds and the histograms, in the plan's shared work buffer.
+ * Synchronises.
+ * fb_channel_moments: out_dev DEVICE double [2][N] = sum over the N^2 pixels of (v - mean_dev[c]) and of (v - mean_dev[c])^2 per
+ * channel c, fp64 in a fixed order (the same bits on every call); mean_dev DEVICE double [N] as fb_channel_means writes it. */
+int fb_minkowski_counts(fb_plan* plan, const void* real, const double* thresholds, int nt, int mode, uint64_t* counts_out,
+                        uint64_t* n_nan_out, void* stream);
+int fb_channel_moments(fb_plan* plan, const void* cube, const double* mean_dev, double* out_dev, void* stream);
+
 /* ---- the steps after the density-field path: foregrounds (fastbox/foregrounds.py:48-175) and radiometer
  * noise (fastbox/noise.py:25-75).  2-D maps are T[N][N] over (x, y); cubes T[N][N][N], frequency axis last. ---- */
 /* realise_foreground_amp (:99-107): map_out = Re ifft2((re + i im) amp2d) + monopole.  amp2d = sqrt(C_ell) per
