@@ -168,6 +168,11 @@ SIGNATURES = {
     "fb_minkowski_counts": (c_int, [c_void_p, c_void_p, P_double, c_int, c_int, ctypes.POINTER(c_u64), ctypes.POINTER(c_u64),
                                     c_void_p]),
     "fb_channel_moments": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fb_tidal_k": (c_int, [c_void_p, c_void_p, ctypes.POINTER(c_void_p), c_double, c_void_p]),
+    "fb_shear_k": (c_int, [c_void_p, ctypes.POINTER(c_void_p), ctypes.POINTER(c_void_p), c_double, c_double, c_void_p]),
+    "fb_web_eigen": (c_int, [c_void_p, ctypes.POINTER(c_void_p), P_double, c_int, c_int, c_void_p, ctypes.POINTER(c_void_p),
+                             c_void_p, ctypes.POINTER(c_u64), P_double, ctypes.POINTER(c_u64), c_void_p]),
+    "fb_web_mask": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "fb_sky_realise_map": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_u64, c_double, c_void_p, c_void_p, c_void_p]),
     "fb_sky_normal_map": (c_int, [c_void_p, c_void_p, c_u64, c_double, c_double, c_void_p, c_void_p]),
     "fb_sky_gaussian_filter": (c_int, [c_void_p, c_void_p, c_void_p, P_double, c_int, c_void_p]),

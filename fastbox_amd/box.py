@@ -1248,6 +1248,28 @@ class CosmoBox(object):
                 raise ValueError("no delta_x: realise_density() first, or pass delta_x")
         return minkowski.minkowski_functionals(delta_x, box=self, **kw)
 
+    # ------------------------------------------------------------ cosmic-web classification
+    def tidal_tensor(self, delta_x=None, delta_k=None, smoothing=0.):
+        """Additive: the tidal tensor of a density on the device, the inverse transforms of k_i k_j / k^2 exp(-k^2 R^2 / 2)
+        delta(k) with R = ``smoothing`` (Mpc), as a ``fastbox_amd.web.TensorField`` (six real DeviceArrays xx, yy, zz, xy, xz,
+        yz; ``trace()``).  ``delta_x`` (default ``self.delta_x``) or ``delta_k``, not both.  Definition and Nyquist rules:
+        ``fastbox_amd.web.tidal_tensor``; DESIGN.md section 4.  The box's state is left as it was."""
+        from . import web
+        return web.tidal_tensor(self, delta_x=delta_x, delta_k=delta_k, smoothing=smoothing)
+
+    def cosmic_web(self, delta_x=None, smoothing=0., threshold=0., kind='tidal', velocity=None, **kw):
+        """Additive: the cosmic web of a field on the device -- every voxel a void, sheet, filament or knot by the number of
+        eigenvalues above ``threshold`` of the tidal tensor of ``delta_x`` (``kind='tidal'``, the T-web; default
+        ``self.delta_x``) or of the shear tensor of ``velocity``, three real cubes in km/s (``kind='shear'``, the V-web), both
+        smoothed with a Gaussian of ``smoothing`` Mpc.  ``threshold``: a number, or up to 16 ascending ones for a scan.
+        Keywords ``weight``, ``return_classes``, ``return_eigenvalues`` as ``fastbox_amd.web.classify``; ``H0`` (km/s/Mpc,
+        default 100 h) with ``kind='shear'``.  Returns a
+        ``fastbox_amd.web.CosmicWeb`` (counts, volume and mass fractions, the class cube and its masks).  ValueError /
+        TypeError name the argument, before any device work; MemoryError if the work memory does not fit.  DESIGN.md
+        section 4.  The box's state is left as it was."""
+        from . import web
+        return web.cosmic_web(self, delta_x=delta_x, smoothing=smoothing, threshold=threshold, kind=kind, velocity=velocity, **kw)
+
     def sigmaR(self, R):
         """RMS of the field smoothed with a top-hat of R Mpc/h, from the binned power
         spectrum (box.py:657-683; scipy's simps is spelled simpson since 1.14)."""

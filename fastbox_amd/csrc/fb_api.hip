@@ -3,6 +3,7 @@
 #include "fb_plan.h"
 #include "fb_api_util.h"
 #include "fb_kshell.h"                   // FB_TWO_PI
+#include "fb_dev.h"                      // jacobi_rotation (fb_eigen.inc)
 #include <dlfcn.h>
 #include <rccl/rccl.h>           // types and prototypes only: the functions are looked up in a dlopen'ed librccl (fb_comm.inc)
 #include <algorithm>

@@ -43,6 +43,19 @@ __device__ __forceinline__ int axis_weights(double u, int window, int N, long lo
     return 3;
 }
 
+// ---- Jacobi rotation --------------------------------------------------------------------------------------------------------
+// (c, s) of J = [[c, s], [-s, c]] in the (p, q) plane with (J^T A J)_pq = 0 (Golub & Van Loan, Alg. 8.4.1: the smaller root);
+// returns t = s / c, with which a_pp' = a_pp - t a_pq and a_qq' = a_qq + t a_pq.  No loop: a NaN goes through as a NaN.
+__device__ __forceinline__ double jacobi_rotation(double app, double aqq, double apq, double& c, double& s) {
+    c = 1.0; s = 0.0;
+    if (apq == 0.0) return 0.0;
+    const double tau = (aqq - app) / (2.0 * apq);
+    const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));     // (tau^2 = inf: t = 0)
+    c = 1.0 / sqrt(1.0 + t * t);
+    s = t * c;
+    return t;
+}
+
 // ---- wave reductions: over the 64 lanes, the result in every lane -----------------------------------------------------------
 // float: six DPP adds (row_shr 1, 2, 4, 8, then row_bcast 15 and 31 carry the row totals forward; lanes a step does not
 // reach add the `old` operand 0), total in lane 63, one v_readlane -- no LDS crossbar round trips.

@@ -20,15 +20,7 @@ __device__ __forceinline__ void jacobi_pair(int n, int r, int k, int& p, int& q)
     else { a = r + k; if (a >= m) a -= m; b = r - k; if (b < 0) b += m; }
     p = a < b ? a : b; q = a < b ? b : a;
 }
-// (c, s) of J = [[c, s], [-s, c]] in the (p, q) plane with (J^T A J)_pq = 0 (Golub & Van Loan, Alg. 8.4.1: the smaller root)
-__device__ __forceinline__ void jacobi_rotation(double app, double aqq, double apq, double& c, double& s) {
-    c = 1.0; s = 0.0;
-    if (apq == 0.0) return;
-    const double tau = (aqq - app) / (2.0 * apq);
-    const double t = (tau >= 0.0 ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));     // (tau^2 = inf: t = 0)
-    c = 1.0 / sqrt(1.0 + t * t);
-    s = t * c;
-}
+using fb::jacobi_rotation;           // fb_dev.h: the per-voxel 3 x 3 solver of fb_web.hip rotates with it too
 // blockIdx.y < n/2: block row `a` of A; else: rows 2 j, 2 j + 1 of V, j = blockIdx.y - n/2.  Thread = pair b (columns).
 __global__ __launch_bounds__(128) void k_jacobi_round(const double* __restrict__ A, double* __restrict__ An,
                                                       const double* __restrict__ V, double* __restrict__ Vn, int n, int r) {

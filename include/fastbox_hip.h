@@ -870,6 +870,35 @@ int fb_minkowski_counts(fb_plan* plan, const void* real, const double* threshold
                         uint64_t* n_nan_out, void* stream);
 int fb_channel_moments(fb_plan* plan, const void* cube, const double* mean_dev, double* out_dev, void* stream);
 
+/* ---- cosmic-web classification: tidal and shear tensors, their eigenvalues and classes (fb_web.hip; definition: DESIGN.md
+ * section 4, numpy statement: tests/web_numpy.py).  One box on one GPU, any box shape, both precisions, every grid the FFT
+ * takes.  Components are in the order xx, yy, zz, xy, xz, yz; pointer arrays are HOST arrays of DEVICE pointers.  With m_a the
+ * signed FFT index (N/2 -> -N/2), k_a = 2 pi m_a / L_a and fp64 multipliers on both plans:
+ * fb_tidal_k: half_out6[c] = k_i k_j / k^2 exp(-k^2 R^2 / 2) delta(k) for the six pairs, from one read of half_in (a half
+ *   spectrum, fb_fft_r2c; kept).  Zero at k = 0; for i != j zero where m_i = -N/2 or m_j = -N/2; the diagonal keeps its Nyquist
+ *   planes.  fb_fft_c2r of each output with scale 1 / N^3 is the component cube.  R >= 0 (Mpc).
+ * fb_shear_k: half_out6[c] = -(i / 2 H0) (k_i v_j(k) + k_j v_i(k)) exp(-k^2 R^2 / 2) from one read of the three velocity
+ *   spectra half_vel3 (kept); the term k_i v_j is zero where m_i = -N/2.  H0 > 0 in the velocity's units per Mpc.
+ *   Both: the six outputs are distinct buffers and none is an input, else FB_ERR_INVALID (pointers are compared for equality:
+ *   buffers that overlap in part are the caller's to avoid).  Asynchronous.
+ * fb_web_eigen: per voxel of the six real cubes comp6 (T[N^3] each) the eigenvalues lambda_1 >= lambda_2 >= lambda_3 by
+ *   cyclic Jacobi in fp64 with a fixed number of sweeps (backward stable: |error| of the order of 2^-53 ||A||_F, equal
+ *   eigenvalues included; no data-dependent loop), and for each of nt thresholds (HOST double, 0 <= nt <= FB_WEB_NT_MAX,
+ *   finite and strictly ascending) the class = the number of eigenvalues > threshold, decided in fp64: 0 void, 1 sheet,
+ *   2 filament, 3 knot.  A voxel with a component that is not finite -- or with finite components so near the largest double
+ *   that the solve overflows -- has three NaN eigenvalues and class 255; it is counted in n_nan_out and in no class.  Outputs, each of which may be NULL: eig3 (HOST array of three DEVICE T[N^3], entries may be
+ *   NULL) the eigenvalues rounded to T; classes DEVICE uint8[N^3] for threshold index class_at; counts_out HOST uint64 [nt][4];
+ *   wsum_out HOST double [nt][4], the sums of weight (DEVICE T[N^3]; NULL: zeros) per class; n_nan_out HOST uint64.  Counts are
+ *   integer sums; weight sums are fp64, per lane, then per workgroup, then over the workgroups, each in a fixed order: the
+ *   same bits on every call.  Work memory: the plan's shared work buffer.  Synchronises if a HOST output is asked for.
+ * fb_web_mask: real_out T[N^3] = 1 where classes (DEVICE uint8[N^3]) == kind (0 .. 3), else 0.  Asynchronous.              */
+#define FB_WEB_NT_MAX 16
+int fb_tidal_k(fb_plan* plan, const void* half_in, void* const* half_out6, double R, void* stream);
+int fb_shear_k(fb_plan* plan, const void* const* half_vel3, void* const* half_out6, double R, double H0, void* stream);
+int fb_web_eigen(fb_plan* plan, const void* const* comp6, const double* thresholds, int nt, int class_at, const void* weight,
+                 void* const* eig3, uint8_t* classes, uint64_t* counts_out, double* wsum_out, uint64_t* n_nan_out, void* stream);
+int fb_web_mask(fb_plan* plan, const uint8_t* classes, int kind, void* real_out, void* stream);
+
 /* ---- the steps after the density-field path: foregrounds (fastbox/foregrounds.py:48-175) and radiometer
  * noise (fastbox/noise.py:25-75).  2-D maps are T[N][N] over (x, y); cubes T[N][N][N], frequency axis last. ---- */
 /* realise_foreground_amp (:99-107): map_out = Re ifft2((re + i im) amp2d) + monopole.  amp2d = sqrt(C_ell) per
