@@ -128,6 +128,7 @@ SIGNATURES = {
     "fb_beam_convolve": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p]),
     "fb_channel_means": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "fb_channel_covariance": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fb_channel_covariance_plan": (c_int, [c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_i64)]),
     "fb_leading_eigenvectors": (c_int, [c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fb_pca_clean": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p]),
     "fb_real_min": (c_int, [c_void_p, c_void_p, P_double, ctypes.POINTER(c_i64), c_void_p]),

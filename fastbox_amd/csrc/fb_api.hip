@@ -590,6 +590,17 @@ int fb_channel_covariance(fb_plan* p, const void* cube, const double* mean_dev, 
     hipStream_t s = (hipStream_t)stream;
     return FB_DISPATCH(p, fbi_channel_cov_f32(p, cube, mean_dev, cov_dev, s), fbi_channel_cov_f64(p, cube, mean_dev, cov_dev, s));
 }
+// host only, no device: the pixel slices fb_channel_covariance launches for a grid of N on a device of num_cu compute units
+int fb_channel_covariance_plan(int N, int num_cu, int* slices_out, int64_t* rows_out) {
+    if (N < 2 || num_cu < 1 || !slices_out || !rows_out) {
+        fb_set_error("covariance plan: N >= 2, num_cu >= 1 and two outputs");
+        return FB_ERR_INVALID;
+    }
+    const FbCovPlan c = fb_channel_cov_plan(N, num_cu);
+    *slices_out = c.slices;
+    *rows_out = (int64_t)c.rows;
+    return FB_OK;
+}
 int fb_pca_clean(fb_plan* p, const void* cube, const double* mean_dev, const double* modes_dev, int nmodes, void* cube_out,
                  double* amps_dev, void* stream) {
     FB_REQUIRE(p && cube && mean_dev && cube_out && (modes_dev || nmodes == 0), "null pointer");

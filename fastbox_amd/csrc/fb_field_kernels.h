@@ -1368,14 +1368,14 @@ typedef double fb_d4 __attribute__((ext_vector_type(4)));
 // and are not stored.
 template <typename T, int MA, bool EDGE = false>
 __global__ __launch_bounds__(64) void k_channel_cov(const T* __restrict__ cube, const double* __restrict__ mean,
-                                                    double* __restrict__ partial, long long npix, int N, int nbs) {
-    // blockIdx.x -> (bi <= bj) pair, blockIdx.y -> pixel slice
+                                                    double* __restrict__ partial, long long npix, long long per, int N,
+                                                    int nbs) {
+    // blockIdx.x -> (bi <= bj) pair, blockIdx.y -> pixel slice of `per` pixels (fb_channel_cov_plan: p0 < npix for every slice)
     int bi = 0, rem = blockIdx.x;
     while (rem >= nbs - bi) { rem -= nbs - bi; ++bi; }
     const int bj = bi + rem;
     const int lane = threadIdx.x, lc = lane & 15, lk = lane >> 4;
     const int a0 = bi * 16 * MA, b0 = bj * 16 * MA;
-    const long long per = ((npix + gridDim.y - 1) / gridDim.y + 3) & ~3LL;
     const long long p0 = (long long)blockIdx.y * per, p1 = p0 + per < npix ? p0 + per : npix;
     double ma[MA], mb[MA];
     int ca[MA], cb[MA];                    // channel of this lane in block row i / block column i
@@ -1400,7 +1400,7 @@ __global__ __launch_bounds__(64) void k_channel_cov(const T* __restrict__ cube, 
 #pragma unroll
         for (int u = 0; u < KU; ++u) {
             const long long row = p + 4 * u + lk;
-            const T* src = cube + (row < p1 ? row : p0) * N;       // past the slice: any valid row, masked below
+            const T* src = cube + (row < p1 ? row : p0) * N;       // past the slice: its first row (p0 < npix), masked below
 #pragma unroll
             for (int i = 0; i < MA; ++i) { fa[buf][u][i] = src[ca[i]]; fb_[buf][u][i] = src[cb[i]]; }
         }

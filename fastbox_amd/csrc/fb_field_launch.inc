@@ -481,25 +481,19 @@ int FBI(channel_means)(fb_plan* p, const void* cube, double* mean_dev, hipStream
 int FBI(channel_cov)(fb_plan* p, const void* cube, const double* mean_dev, double* cov_dev, hipStream_t s) {
     const int N = p->N;
     const long long npix = (long long)N * N;
-    // blocks of 16 MA channels: the largest of 64, 32, 16 that divides N; a grid whose size is no multiple of 16 (18, 30, 50, ...)
-    // takes 16-channel blocks with a masked last one
-    const int MA = N % 64 == 0 ? 4 : (N % 32 == 0 ? 2 : 1);
-    const bool edge = N % 16 != 0;
-    const int bs = 16 * MA, nbs = (N + bs - 1) / bs, npairs = nbs * (nbs + 1) / 2;
-    int slices = (8 * p->num_cu + npairs - 1) / npairs;            // ~8 waves per CU (two rounds of one per SIMD)
-    if (slices > npix / 64) slices = (int)(npix / 64);
-    if (slices < 1) slices = 1;
+    const FbCovPlan c = fb_channel_cov_plan(N, p->num_cu);       // block shape and pixel slices: fb_plan.h
+    const int MA = c.MA, bs = 16 * MA, nbs = c.nbs, slices = c.slices;
     FB_TRY(p->work.ensure((size_t)slices * N * N * sizeof(double)));
     { FbProfScope _ps(p, FBK_PCA, s);
-    const dim3 grid(npairs, slices);
+    const dim3 grid(c.npairs, slices);
     if (MA == 4) hipLaunchKernelGGL((k_channel_cov<real_t, 4>), grid, dim3(64), 0, s, (const real_t*)cube, mean_dev,
-                                    p->work.as<double>(), npix, N, nbs);
+                                    p->work.as<double>(), npix, c.rows, N, nbs);
     else if (MA == 2) hipLaunchKernelGGL((k_channel_cov<real_t, 2>), grid, dim3(64), 0, s, (const real_t*)cube, mean_dev,
-                                         p->work.as<double>(), npix, N, nbs);
-    else if (!edge) hipLaunchKernelGGL((k_channel_cov<real_t, 1>), grid, dim3(64), 0, s, (const real_t*)cube, mean_dev,
-                                       p->work.as<double>(), npix, N, nbs);
+                                         p->work.as<double>(), npix, c.rows, N, nbs);
+    else if (!c.edge) hipLaunchKernelGGL((k_channel_cov<real_t, 1>), grid, dim3(64), 0, s, (const real_t*)cube, mean_dev,
+                                         p->work.as<double>(), npix, c.rows, N, nbs);
     else hipLaunchKernelGGL((k_channel_cov<real_t, 1, true>), grid, dim3(64), 0, s, (const real_t*)cube, mean_dev,
-                            p->work.as<double>(), npix, N, nbs); }
+                            p->work.as<double>(), npix, c.rows, N, nbs); }
     FB_LAUNCH_CHECK("k_channel_cov");
     { FbProfScope _ps(p, FBK_PCA, s);
     hipLaunchKernelGGL(k_cov_finish, dim3((N + 63) / 64, N), dim3(64), 0, s, p->work.as<const double>(), slices, N, bs,

@@ -290,5 +290,26 @@ struct FbProfScope {
                                    double* results, hipStream_t s);
 FB_DECL(f32)
 FB_DECL(f64)
+// The launch plan of k_channel_cov (fbi_channel_cov, fb_channel_covariance_plan): blocks of 16 MA channels -- the largest of
+// 64, 32, 16 that divides N; a grid whose size is no multiple of 16 (18, 30, 50, ...) takes 16-channel blocks with a masked last
+// one -- and the split of the N^2 pixels into `slices` runs of `rows` pixels: about 8 waves per CU (two rounds of one per SIMD)
+// over all block pairs, at least 64 pixels each, `rows` a multiple of 4 (one matrix instruction takes 4 pixels).  Every slice
+// is non-empty and they tile [0, N^2): slice q is [q rows, min((q + 1) rows, N^2)), slices = ceil(N^2 / rows).
+struct FbCovPlan { int MA, nbs, npairs, slices; bool edge; long long rows; };
+inline FbCovPlan fb_channel_cov_plan(int N, int num_cu) {
+    FbCovPlan c;
+    const long long npix = (long long)N * N;
+    c.MA = N % 64 == 0 ? 4 : (N % 32 == 0 ? 2 : 1);
+    c.edge = N % 16 != 0;
+    const int bs = 16 * c.MA;
+    c.nbs = (N + bs - 1) / bs;
+    c.npairs = c.nbs * (c.nbs + 1) / 2;
+    long long want = (8LL * num_cu + c.npairs - 1) / c.npairs;
+    if (want > npix / 64) want = npix / 64;
+    if (want < 1) want = 1;
+    c.rows = ((npix + want - 1) / want + 3) & ~3LL;
+    c.slices = (int)((npix + c.rows - 1) / c.rows);        // <= want: rounding `rows` up can only empty the last of them
+    return c;
+}
 int fbi_bin_count(fb_plan* p, hipStream_t s);
 int fbi_slab_permute(fb_plan* p, const void* in, void* out, int nxl, int nparts, int pack, hipStream_t s);

@@ -609,6 +609,11 @@ int fb_channel_means(fb_plan* plan, const void* cube, double* mean_dev, void* st
  * the fp64 matrix cores (v_mfma_f64_16x16x4_f64) with a fixed summation order.  Its leading eigenvectors
  * (:161-169; an N x N problem): fb_leading_eigenvectors below, or the caller's own solver -- modes_dev[N][nmodes].   */
 int fb_channel_covariance(fb_plan* plan, const void* cube, const double* mean_dev, double* cov_dev, void* stream);
+/* The split of the N^2 pixels that fb_channel_covariance uses on a device of num_cu compute units, on the host and without a
+ * device: slice q of *slices_out covers the pixels [q rows, min((q + 1) rows, N^2)) with rows = *rows_out a multiple of 4; every
+ * slice is non-empty and they tile [0, N^2).  The partial sums of the slices are added in slice order.  FB_ERR_INVALID for
+ * N < 2, num_cu < 1 or a null output.                                                                                      */
+int fb_channel_covariance_plan(int N, int num_cu, int* slices_out, int64_t* rows_out);
 /* The nmodes leading eigenpairs of cov_dev[N][N] (symmetric, fp64, DEVICE; not modified) -- np.linalg.eig + the sort by
  * decreasing eigenvalue of :161-169 -- by cyclic two-sided Jacobi in fp64 on the device (round-robin ordering, N/2
  * rotations per launch; 6-10 sweeps): modes_dev[N][nmodes] (orthonormal columns, the sign of a column is not defined,
