@@ -134,6 +134,8 @@ SIGNATURES = {
     "fb_real_min": (c_int, [c_void_p, c_void_p, P_double, ctypes.POINTER(c_i64), c_void_p]),
     "fb_complex_to_real": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
     "fb_nmf_sweep": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, P_double, c_void_p]),
+    "fb_nmf_sweep_plan": (c_int, [c_int, c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_i64)]),
+    "fb_ica_step_plan": (c_int, [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_i64)]),
     "fb_nmf_residual": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, P_double, c_void_p]),
     "fb_nndsvd_norms": (c_int, [c_void_p, c_void_p, c_int, P_double, c_void_p]),
     "fb_nndsvd_fill": (c_int, [c_void_p, c_void_p, c_int, P_double, c_int, c_double, c_double, c_void_p]),

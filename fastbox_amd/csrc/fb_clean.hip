@@ -14,10 +14,11 @@
 
 #define FB_CLEAN_KMAX 16                 // components (NMF) / sources (ICA)
 #define FB_CLEAN_NMAX 1024               // channels of the NMF sweep: four spectra in fp64 take 32 KiB of LDS
-#define FB_CLEAN_RED_BLOCKS 1024         // workgroups of the grid-stride reductions
+#define FB_CLEAN_RED_BLOCKS 1024         // workgroups of the grid-stride reductions (and the most of fb_ica_step_split)
 
 namespace {
 using namespace fb;
+static_assert(FB_CLEAN_RED_BLOCKS == 1024, "fb_ica_step_split (fb_plan.h) caps the workgroups of k_ica_step at 1024");
 
 // One cyclic coordinate-descent pass over the k coefficients v[] of one row (scikit-learn's _update_cdnmf_fast, no
 // regularisation, no shuffling): b[t] = the row of X H^T (or X^T W), A = H H^T (or W^T W), k x k in LDS.
@@ -57,7 +58,7 @@ __global__ __launch_bounds__(256) void k_nmf_gram(const double* __restrict__ M, 
 template <typename T, int CPL>
 __global__ __launch_bounds__(256) void k_nmf_sweep(const T* __restrict__ cube, double* __restrict__ W, const double* __restrict__ H,
                                                    const double* __restrict__ HHt, int k, long long npix, int N,
-                                                   double* __restrict__ partial) {
+                                                   long long per, double* __restrict__ partial) {
     extern __shared__ double lds[];
     double* A = lds;                                  // [k][k]
     double* ws = lds + FB_CLEAN_KMAX * FB_CLEAN_KMAX; // [4][16]
@@ -65,8 +66,7 @@ __global__ __launch_bounds__(256) void k_nmf_sweep(const T* __restrict__ cube, d
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     if ((int)threadIdx.x < k * k) A[threadIdx.x] = HHt[threadIdx.x];
     __syncthreads();
-    const long long per = ((npix + gridDim.x - 1) / gridDim.x + 3) & ~3LL;
-    const long long p0 = (long long)blockIdx.x * per, p1 = p0 + per < npix ? p0 + per : npix;
+    const long long p0 = (long long)blockIdx.x * per, p1 = p0 + per < npix ? p0 + per : npix;     // per: fb_nmf_sweep_split
     double acc[CPL][4];
 #pragma unroll
     for (int q = 0; q < CPL; ++q)
@@ -292,11 +292,11 @@ __device__ __forceinline__ void ica_g(int fun, double alpha, double y, double& g
 // n-vector in registers: n + 1 accumulators per thread instead of n^2 + n.  The 16 pixel lanes of a row are then added in
 // lane order through LDS.
 __global__ __launch_bounds__(256) void k_ica_step(const double* __restrict__ Wm, const double* __restrict__ X1, int n,
-                                                  long long npix, int fun, double alpha, double* __restrict__ partial) {
+                                                  long long npix, long long per, int fun, double alpha,
+                                                  double* __restrict__ partial) {
     __shared__ double sh[16][16][FB_CLEAN_KMAX + 1];
     const int i = threadIdx.x >> 4, l = threadIdx.x & 15;
-    const long long per = (npix + gridDim.x - 1) / gridDim.x;
-    const long long p0 = (long long)blockIdx.x * per, p1 = p0 + per < npix ? p0 + per : npix;
+    const long long p0 = (long long)blockIdx.x * per, p1 = p0 + per < npix ? p0 + per : npix;     // per: fb_ica_step_split
     double wrow[FB_CLEAN_KMAX], acc[FB_CLEAN_KMAX], agp = 0.0;
 #pragma unroll
     for (int j = 0; j < FB_CLEAN_KMAX; ++j) { wrow[j] = (i < n && j < n) ? Wm[i * n + j] : 0.0; acc[j] = 0.0; }
@@ -417,8 +417,8 @@ int nmf_sweep(fb_plan* p, const void* cube, double* W, double* H, int k, double*
     const int N = p->N;
     const long long npix = (long long)N * N;
     if (N > FB_CLEAN_NMAX) { fb_set_error("fb_nmf_sweep: at most 1024 channels"); return FB_ERR_UNSUPPORTED; }
-    long long nb = (npix + 3) / 4;
-    if (nb > 2LL * p->num_cu) nb = 2LL * p->num_cu;
+    const FbPixelSplit split = fb_nmf_sweep_split(N, p->num_cu);
+    const long long nb = split.workgroups;
     const size_t m = (size_t)N * k + (size_t)k * k + 1;
     // work: [H H^T: 256 | finished sums: m | violations: 2 | partials: nb m]
     const size_t head = 256 + m + 2;
@@ -432,7 +432,7 @@ int nmf_sweep(fb_plan* p, const void* cube, double* W, double* H, int k, double*
     hipLaunchKernelGGL(k_nmf_gram, dim3(1), dim3(256), 0, s, (const double*)H, k, N, hht);
 #define FB_NMF_CASE(C_)                                                                                                    \
     hipLaunchKernelGGL((k_nmf_sweep<T, C_>), dim3((unsigned)nb), dim3(256), lds, s, (const T*)cube, W, (const double*)H,   \
-                       (const double*)hht, k, npix, N, partial)
+                       (const double*)hht, k, npix, N, split.per, partial)
     switch (channels_per_lane(N)) {
         case 1: FB_NMF_CASE(1); break;
         case 2: FB_NMF_CASE(2); break;
@@ -546,6 +546,28 @@ int fb_complex_to_real(fb_plan* p, const void* full_cube, void* real_cube, void*
     return FB_OK;
 }
 
+// host only, no device: the pixel partitions of k_nmf_sweep on a device of num_cu compute units and of k_ica_step
+int fb_nmf_sweep_plan(int N, int num_cu, int* workgroups_out, int64_t* pixels_out) {
+    if (N < 2 || N > FB_CLEAN_NMAX || num_cu < 1 || !workgroups_out || !pixels_out) {
+        fb_set_error("NMF sweep plan: 2 <= N <= 1024, num_cu >= 1 and two outputs");
+        return FB_ERR_INVALID;
+    }
+    const FbPixelSplit c = fb_nmf_sweep_split(N, num_cu);
+    *workgroups_out = c.workgroups;
+    *pixels_out = (int64_t)c.per;
+    return FB_OK;
+}
+int fb_ica_step_plan(int N, int* workgroups_out, int64_t* pixels_out) {
+    if (N < 2 || !workgroups_out || !pixels_out) {
+        fb_set_error("ICA step plan: N >= 2 and two outputs");
+        return FB_ERR_INVALID;
+    }
+    const FbPixelSplit c = fb_ica_step_split(N);
+    *workgroups_out = c.workgroups;
+    *pixels_out = (int64_t)c.per;
+    return FB_OK;
+}
+
 int fb_nmf_sweep(fb_plan* p, const void* cube, double* W_dev, double* H_dev, int k, double* violation_out, void* stream) {
     FB_REQUIRE(p && cube && W_dev && H_dev && violation_out, "null pointer");
     FB_REQUIRE(k >= 1 && k <= FB_CLEAN_KMAX, "the number of components must lie in 1 .. 16");
@@ -618,8 +640,8 @@ int fb_ica_step(fb_plan* p, const double* W, const double* X1_dev, int n, int fu
     FB_USE_DEVICE(p);
     hipStream_t s = (hipStream_t)stream;
     const long long npix = (long long)p->N * p->N;
-    long long nb = (npix + 63) / 64;
-    if (nb > FB_CLEAN_RED_BLOCKS) nb = FB_CLEAN_RED_BLOCKS;
+    const FbPixelSplit split = fb_ica_step_split(p->N);
+    const long long nb = split.workgroups;
     const int m = n * n + n;
     // work: [W: 256 | result: m | partials: nb m]
     FB_TRY(p->work.ensure((size_t)(256 + m + nb * m) * sizeof(double)));
@@ -627,7 +649,8 @@ int fb_ica_step(fb_plan* p, const double* W, const double* X1_dev, int n, int fu
     double* res = wdev + 256;
     FB_HIP(hipMemcpyAsync(wdev, W, (size_t)n * n * sizeof(double), hipMemcpyHostToDevice, s));
     { FbProfScope _ps(p, FBK_PCA, s);
-    hipLaunchKernelGGL(k_ica_step, dim3((unsigned)nb), dim3(256), 0, s, (const double*)wdev, X1_dev, n, npix, fun, alpha, res + m);
+    hipLaunchKernelGGL(k_ica_step, dim3((unsigned)nb), dim3(256), 0, s, (const double*)wdev, X1_dev, n, npix, split.per, fun,
+                       alpha, res + m);
     sum_rows(res + m, (int)nb, m, 1.0 / (double)npix, res, s); }
     FB_LAUNCH_CHECK("k_ica_step");
     double h[FB_CLEAN_KMAX * FB_CLEAN_KMAX + FB_CLEAN_KMAX];

@@ -311,5 +311,22 @@ inline FbCovPlan fb_channel_cov_plan(int N, int num_cu) {
     c.slices = (int)((npix + c.rows - 1) / c.rows);        // <= want: rounding `rows` up can only empty the last of them
     return c;
 }
+// The pixel partitions of k_nmf_sweep (nmf_sweep, fb_nmf_sweep_plan) and of k_ica_step (fb_ica_step, fb_ica_step_plan):
+// workgroup q takes the pixels [q per, min((q + 1) per, N^2)).  Trailing workgroups whose share starts at or past N^2 are empty:
+// they read no pixel and write a partial of zeros.  The sweep walks four pixels at a time (one per wave): two workgroups per CU,
+// `per` a multiple of 4.  The ICA step: about 64 pixels per workgroup, at most 1024 workgroups (FB_CLEAN_RED_BLOCKS).
+struct FbPixelSplit { int workgroups; long long per; };
+inline FbPixelSplit fb_nmf_sweep_split(int N, int num_cu) {
+    const long long npix = (long long)N * N;
+    long long nb = (npix + 3) / 4;
+    if (nb > 2LL * num_cu) nb = 2LL * num_cu;
+    return FbPixelSplit{(int)nb, ((npix + nb - 1) / nb + 3) & ~3LL};
+}
+inline FbPixelSplit fb_ica_step_split(int N) {
+    const long long npix = (long long)N * N;
+    long long nb = (npix + 63) / 64;
+    if (nb > 1024) nb = 1024;
+    return FbPixelSplit{(int)nb, (npix + nb - 1) / nb};
+}
 int fbi_bin_count(fb_plan* p, hipStream_t s);
 int fbi_slab_permute(fb_plan* p, const void* in, void* out, int nxl, int nparts, int pack, hipStream_t s);

@@ -654,6 +654,12 @@ int fb_complex_to_real(fb_plan* plan, const void* full_cube, void* real_cube, vo
  *   X^T X, B has nearly orthogonal columns, so that the singular values and vectors of X follow from this matrix without the
  *   loss of the Gram matrix.  work_dev: N^3 + N doubles.                                              */
 int fb_nmf_sweep(fb_plan* plan, const void* cube, double* W_dev, double* H_dev, int k, double* violation_out, void* stream);
+/* The pixel partitions of fb_nmf_sweep (on a device of num_cu compute units) and of fb_ica_step, on the host and without a device:
+ * workgroup q of *workgroups_out takes the pixels [q per, min((q + 1) per, N^2)), per = *pixels_out; a workgroup whose share starts
+ * at or past N^2 is empty and contributes zeros.  The workgroups' partial sums are added in workgroup order.  The sweep's `per` is
+ * a multiple of 4.  FB_ERR_INVALID for N < 2 (the sweep: N > 1024), num_cu < 1 or a null output.                              */
+int fb_nmf_sweep_plan(int N, int num_cu, int* workgroups_out, int64_t* pixels_out);
+int fb_ica_step_plan(int N, int* workgroups_out, int64_t* pixels_out);
 int fb_nmf_residual(fb_plan* plan, const void* cube, const double* W_dev, const double* H_dev, int k, void* cube_out,
                     double* sumsq_out, void* stream);
 int fb_nndsvd_norms(fb_plan* plan, const double* amps_dev, int k, double* out, void* stream);
