@@ -28,5 +28,7 @@ from . import minkowski                           # noqa: F401
 from .minkowski import MinkowskiFunctionals, minkowski_functionals   # noqa: F401
 from . import web                                 # noqa: F401
 from .web import CosmicWeb, TensorField           # noqa: F401
+from . import interferometer                      # noqa: F401
+from .interferometer import Interferometer, UVCoverage, Observation   # noqa: F401
 
 __version__ = "0.1.0"

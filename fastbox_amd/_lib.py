@@ -181,6 +181,9 @@ SIGNATURES = {
     "fb_sky_gaussian_filter": (c_int, [c_void_p, c_void_p, c_void_p, P_double, c_int, c_void_p]),
     "fb_sky_foreground_cube": (c_int, [c_void_p, c_void_p, c_void_p, c_double, P_double, c_void_p, c_void_p]),
     "fb_sky_noise_cube": (c_int, [c_void_p, P_double, c_void_p, c_u64, c_void_p, c_void_p]),
+    "fb_uv_coverage": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "fb_uv_channel_sums": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),
+    "fb_uv_weight": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p]),
     "fb_slab_half_bytes": (c_i64, [c_void_p, c_int]),
     "fb_slab_kspace_bytes": (c_i64, [c_void_p, c_int]),
     "fb_slab_forward_local": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_void_p]),

@@ -932,6 +932,27 @@ int fb_sky_foreground_cube(fb_plan* plan, const void* amps, const void* alpha, d
 int fb_sky_noise_cube(fb_plan* plan, const double* sigma, const void* unit, uint64_t seed, void* cube_out,
                       void* stream);
 
+/* ---- interferometer: uv coverage of a set of projected baselines per channel, and the weighting of a transformed cube
+ * (fastbox_amd/interferometer.py).  N even; cubes are [N][N][N] with the frequency channel c last; mode
+ * index i of a transverse axis stands for the signed mode i (i <= N/2) or i - N.
+ * fb_uv_coverage: samples_dev DEVICE double [ns][2], projected baselines (bx, by) in metres; mult_dev DEVICE int32 [ns]
+ *   multiplicities >= 1 (NULL: all 1); sx_dev, sy_dev DEVICE double [N], cells per metre in channel c.  For sample s and
+ *   channel c, in fp64: a = rint(bx sx[c]), b = rint(by sy[c]) (one multiply, one round-half-to-even each); the sample is
+ *   accepted iff |a| <= N/2 and |b| <= N/2, and then adds m to counts[a mod N][b mod N][c] and m to
+ *   counts[-a mod N][-b mod N][c] (the conjugate visibility of a real sky; a self-conjugate cell receives 2 m).  counts_dev
+ *   DEVICE int32 [N][N][N], zeroed first unless accumulate = 1; the caller keeps 2 sum(m) <= 2^31 - 1.  Integer atomic adds:
+ *   the same bits on every call.  ns = 0 is legal.  Asynchronous.
+ * fb_uv_channel_sums: out_dev DEVICE int64 [2][N]: out[0][c] = sum of counts[.][.][c], out[1][c] = the number of cells of
+ *   channel c with a count > 0.  Integer sums.  Asynchronous.
+ * fb_uv_weight: full_cube_inout (complex T[N][N][N]) [x][y][c] *= f(counts[x][y][c]) scale_dev[c]; f(S) = S (mode 0),
+ *   [S > 0] (1) or sqrt(S) (2); scale_dev DEVICE double [N].  The factor f scale is formed in fp64; each component is
+ *   multiplied by it in fp64 and rounded once to T.  Asynchronous.                                                          */
+int fb_uv_coverage(fb_plan* plan, const double* samples_dev, const int32_t* mult_dev, int64_t ns, const double* sx_dev,
+                   const double* sy_dev, int32_t* counts_dev, int accumulate, void* stream);
+int fb_uv_channel_sums(fb_plan* plan, const int32_t* counts_dev, int64_t* out_dev, void* stream);
+int fb_uv_weight(fb_plan* plan, void* full_cube_inout, const int32_t* counts_dev, int mode, const double* scale_dev,
+                 void* stream);
+
 /* ---- slab-decomposed 3-D FFT for one box spread over `nparts` GPUs (one process per GPU) ---------
  * Rank `part` owns x-planes [part*N/nparts, ...) of real fields (T[N/nparts][N][N]) and, in k space,
  * k_y rows [part*N/nparts, ...) of every x-plane: kslab = complex<T>[N][N/nparts][pitch].
