@@ -32,10 +32,7 @@ def _result(eng, buf, shape):
     """A buffer of the plan's reals as a REAL DeviceArray where the shape is the box's, else as a host fp64 array."""
     if tuple(shape) == (eng.N,) * 3:
         return DeviceArray(eng, REAL, buf)
-    h = np.empty(shape, dtype=eng.rdtype)
-    if h.size:
-        _lib.call("fb_memcpy_d2h", h.ctypes.data_as(ctypes.c_void_p), buf.ptr, h.nbytes, eng.stream)
-    return h.astype(np.float64)
+    return eng.download_raw(buf, shape, eng.rdtype).astype(np.float64)
 
 
 def interpolate_onto_grid(field, coords_orig, coords_new, box=None, indexing='xy'):
@@ -175,10 +172,7 @@ def grid_catalogue(x, y=None, z=None, w=None, xlim=None, ylim=None, zlim=None, n
     ncell = nbin[0] * nbin[1] * nbin[2]
     item = np.dtype(eng.rdtype).itemsize
     need = ncell * (2 * item + item) + (24 * n if pos is not None else 0) + (8 * n if wh is not None else 0)
-    have = eng.free_bytes()
-    if need > have:
-        raise MemoryError("grid_catalogue: %d x %d x %d cells and %d particles take %.2f GiB of work memory, %.2f GiB are free"
-                          % (tuple(nbin) + (n, need / 2. ** 30, have / 2. ** 30)))
+    eng.need_memory(need, "grid_catalogue: %d x %d x %d cells and %d particles take" % (tuple(nbin) + (n,)))
     if pos is not None:
         pptr = None
         if n:

@@ -171,6 +171,36 @@ class DeviceArray(NDArrayOperatorsMixin):
         return "DeviceArray(kind=%s, shape=%s, precision=%s)" % (self.kind, self.shape, self.engine.precision)
 
 
+class DeviceBuffer(object):
+    """A device buffer of one shape and dtype with a lazily cached, read-only host copy: the base of the result classes
+    the feature modules return (catalogues, labels, counts).  ``np.asarray(b)`` is the host copy."""
+
+    def __init__(self, engine, buf, shape, dtype):
+        self.engine, self._buf = engine, buf
+        self.shape, self.dtype = tuple(int(s) for s in shape), np.dtype(dtype)
+        self.ndim = len(self.shape)
+        self.size = int(np.prod(self.shape, dtype=np.int64))
+        self._host = None
+
+    @property
+    def ptr(self):
+        return self._buf.ptr if self._buf is not None else None
+
+    def __len__(self):
+        return self.shape[0]
+
+    def host(self):
+        if self._host is None:
+            h = self.engine.download_raw(self._buf, self.shape, self.dtype)     # (no device call for an empty shape)
+            h.setflags(write=False)
+            self._host = h
+        return self._host
+
+    def __array__(self, dtype=None, copy=None):
+        h = self.host()
+        return h if dtype is None or np.dtype(dtype) == h.dtype else h.astype(dtype)
+
+
 def new_stream(device=None, priority=None):
     """A fresh non-blocking HIP stream (raw handle) for ``CosmoBox(..., stream=...)``: independent
     boxes on different streams overlap on the GPU (compute-bound passes of one with memory-bound
@@ -314,14 +344,27 @@ class Engine(object):
         _lib.call("fb_memcpy_h2d", buf.ptr, _ptr(a), a.nbytes, self.stream)
         return buf
 
+    def download_raw(self, src, shape, dtype=np.float64, offset=0):
+        """Device memory -> a new host array of the given shape and dtype, as stored.  ``src``: a buffer (anything with
+        ``.ptr``) or a raw device pointer; ``offset``: bytes from its start.  The copy waits for the stream; an empty array
+        is returned without a device call."""
+        h = np.empty(shape, dtype=dtype)
+        if h.size:
+            _lib.call("fb_memcpy_d2h", _ptr(h), getattr(src, "ptr", src) + offset, h.nbytes, self.stream)
+        return h
+
+    def need_memory(self, nbytes, what):
+        """MemoryError, opening with the caller's phrase ``what``, unless ``nbytes`` of work memory are free."""
+        have = self.free_bytes()
+        if nbytes > have:
+            raise MemoryError("%s %.2f GiB of work memory, %.2f GiB are free" % (what, nbytes / 2. ** 30, have / 2. ** 30))
+
     def download(self, d):
         N = self.N
         if d.kind == HALF:
             full = self.expand_half(d)
             return self.download(full)
-        dt = self.rdtype if d.kind == REAL else self.cdtype
-        h = np.empty((N, N, N), dtype=dt)
-        _lib.call("fb_memcpy_d2h", _ptr(h), d.ptr, h.nbytes, self.stream)
+        h = self.download_raw(d, (N, N, N), self.rdtype if d.kind == REAL else self.cdtype)
         return h.astype(np.float64 if d.kind == REAL else np.complex128)
 
     def download_plane(self, d, ix):
@@ -329,16 +372,11 @@ class Engine(object):
         N = self.N
         if d.kind != REAL or not 0 <= ix < N:
             raise ValueError("download_plane: a real field and 0 <= ix < N")
-        h = np.empty((N, N), dtype=self.rdtype)
-        _lib.call("fb_memcpy_d2h", _ptr(h), d.ptr + ix * h.nbytes, h.nbytes, self.stream)
-        _lib.call("fb_stream_sync", self.stream)
-        return h
+        return self.download_raw(d, (N, N), self.rdtype, ix * N * N * np.dtype(self.rdtype).itemsize)
 
     def download_half_raw(self, d):
         """Half spectrum as stored, (N, N, pitch) complex; columns >= N/2+1 are padding."""
-        h = np.empty((self.N, self.rows, self.pitch), dtype=self.cdtype)
-        _lib.call("fb_memcpy_d2h", _ptr(h), d.ptr, h.nbytes, self.stream)
-        return h[:, :self.N, :]
+        return self.download_raw(d, (self.N, self.rows, self.pitch), self.cdtype)[:, :self.N, :]
 
     def clone(self, d):
         out = self.empty(d.kind, d._as_complex)
@@ -674,8 +712,7 @@ class Engine(object):
                     raise RuntimeError("result record overwritten (not registered with register_waiter)")
                 h = self._res_host[res.serial % self.RES_SLOTS]
         else:
-            h = np.empty(2 * nbins + 1)
-            _lib.call("fb_memcpy_d2h", _ptr(h), res.ptr, h.nbytes, self.stream)
+            h = self.download_raw(res, 2 * nbins + 1)
         return h[0:2 * nbins:2].copy(), h[1:2 * nbins:2].copy(), float(h[2 * nbins])
 
     def bin_counts(self):

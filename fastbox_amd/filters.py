@@ -79,8 +79,7 @@ def pca_filter(field, nmodes, fit_powerlaw=False, return_filter=False, box=None,
         # what is added back; np.cov(x) (:157-158) still centres every channel on its own mean, so the covariance
         # is taken about the TRUE channel means -- the fit only enters the projection step (N numbers: host)
         from scipy.optimize import curve_fit
-        h = np.empty(N)
-        _lib.call("fb_memcpy_d2h", h.ctypes.data_as(ctypes.c_void_p), mean_true.ptr, h.nbytes, eng.stream)
+        h = eng.download_raw(mean_true, N)
         freqs = np.linspace(1., 10., N)
 
         def fn(nu, amp, beta):
@@ -98,8 +97,7 @@ def pca_filter(field, nmodes, fit_powerlaw=False, return_filter=False, box=None,
         U_dev = eng._alloc_bytes(max(1, nmodes) * N * 8)
         _lib.call("fb_leading_eigenvectors", eng._plan, cov_dev.ptr, nmodes, U_dev.ptr, None, None, eng.stream)
     else:
-        cov = np.empty((N, N))
-        _lib.call("fb_memcpy_d2h", cov.ctypes.data_as(ctypes.c_void_p), cov_dev.ptr, cov.nbytes, eng.stream)
+        cov = eng.download_raw(cov_dev, (N, N))
         with _few_blas_threads():
             if 0 < nmodes < N:
                 from scipy.linalg import eigh      # only the nmodes largest eigenpairs (LAPACK dsyevr)
@@ -114,13 +112,9 @@ def pca_filter(field, nmodes, fit_powerlaw=False, return_filter=False, box=None,
               amps_dev.ptr if amps_dev is not None else None, eng.stream)
     if not return_filter:
         return out
-    fg_amps = np.empty((nmodes, N * N))
-    if nmodes:
-        _lib.call("fb_memcpy_d2h", fg_amps.ctypes.data_as(ctypes.c_void_p), amps_dev.ptr, fg_amps.nbytes, eng.stream)
+    fg_amps = eng.download_raw(amps_dev, (nmodes, N * N))
     if U_fg is None:
-        U_fg = np.empty((N, nmodes))
-        if nmodes:
-            _lib.call("fb_memcpy_d2h", U_fg.ctypes.data_as(ctypes.c_void_p), U_dev.ptr, U_fg.nbytes, eng.stream)
+        U_fg = eng.download_raw(U_dev, (N, nmodes))
     return out, U_fg, fg_amps
 
 
@@ -146,12 +140,6 @@ def angular_bandpass_filter(field, kmin, kmax, d=1., box=None):
     _lib.call("fb_fft_transverse", eng._plan, cube.ptr, +1, eng.stream)
     cube.invalidate()
     return cube
-
-
-def _download(eng, buf, shape):
-    h = np.empty(shape)
-    _lib.call("fb_memcpy_d2h", h.ctypes.data_as(ctypes.c_void_p), buf.ptr, h.nbytes, eng.stream)
-    return h
 
 
 def _check_nmodes(nmodes):
@@ -191,7 +179,7 @@ class NMFResult(object):
 
     def W_host(self):
         k = self.n_components_
-        return np.ascontiguousarray(_download(self.engine, self.W, (k, self.engine.N ** 2)).T)
+        return np.ascontiguousarray(self.engine.download_raw(self.W, (k, self.engine.N ** 2)).T)
 
 
 def _nndsvda(eng, cube, k, eps=1e-6):
@@ -207,14 +195,14 @@ def _nndsvda(eng, cube, k, eps=1e-6):
     mean_dev = _channel_means(eng, cube)
     cov_dev = eng._alloc_bytes(N * N * 8)
     _lib.call("fb_channel_covariance", eng._plan, cube.ptr, mean_dev.ptr, cov_dev.ptr, eng.stream)
-    mean, cov = _download(eng, mean_dev, (N,)), _download(eng, cov_dev, (N, N))
+    mean, cov = eng.download_raw(mean_dev, (N,)), eng.download_raw(cov_dev, (N, N))
     gram = (npix - 1.) * cov + npix * np.outer(mean, mean)
     with _few_blas_threads():
         v = np.linalg.eigh(gram)[1][:, ::-1]
     work = eng._alloc_bytes((N * N * N + N) * 8)
     _lib.call("fb_rotated_covariance", eng._plan, cube.ptr, eng.upload_raw(np.ascontiguousarray(v.T)).ptr, work.ptr, cov_dev.ptr,
               eng.stream)
-    gram = _download(eng, cov_dev, (N, N)) * (npix - 1.)                # B^T B
+    gram = eng.download_raw(cov_dev, (N, N)) * (npix - 1.)                # B^T B
     del work
     d = np.sqrt(np.diag(gram))
     d[d == 0.] = 1.
@@ -303,7 +291,7 @@ def nmf_filter(field, nmodes, return_filter=False, box=None, **kwargs_nmf):
               eng.stream)
     if not return_filter:
         return out
-    return out, NMFResult(eng, _download(eng, H, (nmodes, N)), W, n_iter, float(np.sqrt(ss.value)), viols)
+    return out, NMFResult(eng, eng.download_raw(H, (nmodes, N)), W, n_iter, float(np.sqrt(ss.value)), viols)
 
 
 class ICAResult(object):
@@ -318,7 +306,7 @@ class ICAResult(object):
 
     def sources_host(self):
         n = self.components_.shape[0]
-        return np.ascontiguousarray(_download(self.engine, self.sources, (n, self.engine.N ** 2)).T)
+        return np.ascontiguousarray(self.engine.download_raw(self.sources, (n, self.engine.N ** 2)).T)
 
 
 _ICA_FUN = {"logcosh": 0, "exp": 1, "cube": 2}           # FB_ICA_LOGCOSH, FB_ICA_EXP, FB_ICA_CUBE
@@ -372,7 +360,7 @@ def ica_filter(field, nmodes, return_filter=False, box=None, eigensolver="host",
     mean_dev = _channel_means(eng, cube)
     cov_dev = eng._alloc_bytes(N * N * 8)
     _lib.call("fb_channel_covariance", eng._plan, cube.ptr, mean_dev.ptr, cov_dev.ptr, eng.stream)
-    mean, cov = _download(eng, mean_dev, (N,)), _download(eng, cov_dev, (N, N))
+    mean, cov = eng.download_raw(mean_dev, (N,)), eng.download_raw(cov_dev, (N, N))
     lam = np.einsum("ci,cd,di->i", U, cov, U)
     d = np.sqrt(lam * (npix - 1.))
     u = U * np.sign(U[0])

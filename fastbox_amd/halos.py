@@ -22,43 +22,19 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .device import DeviceArray, REAL
+from .device import DeviceArray, DeviceBuffer, REAL
 
 LAM_MAX = float(2 ** 24)
 WINDOWS = {"ngp": 0, "cic": 1, "tsc": 2}
 _SCALAR, _ZPROFILE, _FIELD, _FIELD_F64 = 0, 1, 2, 3
 
 
-class HaloCatalogue(object):
+class HaloCatalogue(DeviceBuffer):
     """Halo positions (comoving, Mpc) on the device: fp64 [Nh][3].  ``np.asarray(cat)`` is the (Nh, 3) array."""
 
     def __init__(self, engine, buf, n):
-        self.engine, self._buf, self.n = engine, buf, int(n)
-        self._host = None
-
-    @property
-    def ptr(self):
-        return self._buf.ptr if self._buf is not None else None
-
-    def __len__(self):
-        return self.n
-
-    @property
-    def shape(self):
-        return (self.n, 3)
-
-    def host(self):
-        if self._host is None:
-            h = np.empty((self.n, 3), dtype=np.float64)
-            if self.n:
-                _lib.call("fb_memcpy_d2h", h.ctypes.data_as(ctypes.c_void_p), self.ptr, h.nbytes, self.engine.stream)
-            h.setflags(write=False)
-            self._host = h
-        return self._host
-
-    def __array__(self, dtype=None, copy=None):
-        h = self.host()
-        return h if dtype is None or np.dtype(dtype) == h.dtype else h.astype(dtype)
+        self.n = int(n)
+        DeviceBuffer.__init__(self, engine, buf, (self.n, 3), np.float64)
 
     def __repr__(self):
         return "HaloCatalogue(%d halos)" % self.n
@@ -135,9 +111,7 @@ class HaloDistribution(object):
         args = self._args(delta_x, nbar, bias, keep)
         buf = eng._alloc_bytes(8 * N ** 3)
         _lib.call("fb_halo_lambda", eng._plan, *args, int(bool(lognormal)), buf.ptr, eng.stream)
-        lam = np.empty((N, N, N), dtype=np.float64)
-        _lib.call("fb_memcpy_d2h", lam.ctypes.data_as(ctypes.c_void_p), buf.ptr, lam.nbytes, eng.stream)
-        return lam
+        return eng.download_raw(buf, (N, N, N))
 
     def halo_count_field(self, delta_x, nbar, bias, lognormal=False, realisation=None):
         """Poisson halo counts per voxel (halos.py:53-117): lam = voxel_vol * nbar * (1 + delta_h), delta_h = bias * delta_x or,
@@ -212,35 +186,12 @@ FOF_TILE = 64                       # particles per LDS tile of the pair search 
 RHO_CRIT = 2.77536627e11            # critical density today in h^2 Msun / Mpc^3
 
 
-class DeviceLabels(object):
+class DeviceLabels(DeviceBuffer):
     """int32 per particle on the device; ``np.asarray(labels)`` is the host copy."""
 
     def __init__(self, engine, buf, n):
-        self.engine, self._buf, self.n = engine, buf, int(n)
-        self._host = None
-
-    @property
-    def ptr(self):
-        return self._buf.ptr if self._buf is not None else None
-
-    def __len__(self):
-        return self.n
-
-    shape = property(lambda self: (self.n,))
-    dtype = np.dtype(np.int32)
-
-    def host(self):
-        if self._host is None:
-            h = np.empty(self.n, dtype=np.int32)
-            if self.n:
-                _lib.call("fb_memcpy_d2h", h.ctypes.data_as(ctypes.c_void_p), self.ptr, h.nbytes, self.engine.stream)
-            h.setflags(write=False)
-            self._host = h
-        return self._host
-
-    def __array__(self, dtype=None, copy=None):
-        h = self.host()
-        return h if dtype is None or np.dtype(dtype) == h.dtype else h.astype(dtype)
+        self.n = int(n)
+        DeviceBuffer.__init__(self, engine, buf, (self.n,), np.int32)
 
 
 class FoFHalos(HaloCatalogue):
@@ -341,10 +292,8 @@ def find_halos_fof(box, particles, linking_length=0.2, nmin=20, absolute=False, 
     if n == 0:
         return empty(0, DeviceLabels(eng, None, 0))
     cells = fof_cells(L, ell, n)
-    need, have = fof_device_bytes(n, cells, nmin, host, has_vel), eng.free_bytes()
-    if need > have:
-        raise MemoryError("find_halos_fof: %d particles in %d x %d x %d cells take %.2f GiB of work memory, %.2f GiB are free"
-                          % ((n,) + cells + (need / 2. ** 30, have / 2. ** 30)))
+    eng.need_memory(fof_device_bytes(n, cells, nmin, host, has_vel),
+                    "find_halos_fof: %d particles in %d x %d x %d cells take" % ((n,) + cells))
     if host:
         pbuf = eng.upload_raw(p)
         keep.append(pbuf)
@@ -376,10 +325,7 @@ def find_halos_fof(box, particles, linking_length=0.2, nmin=20, absolute=False, 
         _lib.call("fb_fof_sizes", eng._plan, root.ptr, n, nmin, small.ptr, count.ptr, kept.ptr if cap else None, out, eng.stream)
         ngroups, nk = int(out[0]), int(out[1])
         del count
-        pairs = np.empty((nk, 2), dtype=np.uint32)
-        if nk:
-            _lib.call("fb_memcpy_d2h", pairs.ctypes.data_as(ctypes.c_void_p), kept.ptr, pairs.nbytes, eng.stream)
-            eng.sync()
+        pairs = eng.download_raw(kept, (nk, 2), np.uint32)
         del kept
         order = np.lexsort((pairs[:, 0], -pairs[:, 1].astype(np.int64)))
         sroots, scounts = np.ascontiguousarray(pairs[order, 0]), np.ascontiguousarray(pairs[order, 1])
@@ -574,10 +520,8 @@ def pair_counts(box, first, second=None, edges=None, mode='1d', Nmu=10, pimax=No
     nr = e.size - 1
     nbins = nr * nsub
     cells = pair_cells(L, reach, max(n1, n2, 1))
-    need, have = pair_device_bytes(n1, 0 if auto else n2, cells, nbins, h1 is not None, h2 is not None), eng.free_bytes()
-    if need > have:
-        raise MemoryError("pair_counts: %d and %d particles in %d x %d x %d cells take %.2f GiB of work memory, %.2f GiB are free"
-                          % ((n1, n2) + cells + (need / 2. ** 30, have / 2. ** 30)))
+    eng.need_memory(pair_device_bytes(n1, 0 if auto else n2, cells, nbins, h1 is not None, h2 is not None),
+                    "pair_counts: %d and %d particles in %d x %d x %d cells take" % ((n1, n2) + cells))
     keep = []
 
     def pointer(n, host, cat):
@@ -602,9 +546,7 @@ def pair_counts(box, first, second=None, edges=None, mode='1d', Nmu=10, pimax=No
               ms if timings is not None else None, eng.stream)
     if bad.value:
         raise ValueError("pair_counts: a position is not finite, or too large to wrap into the box")
-    counts = np.empty(nbins, dtype=np.uint64)
-    _lib.call("fb_memcpy_d2h", counts.ctypes.data_as(ctypes.c_void_p), out.ptr, counts.nbytes, eng.stream)
-    eng.sync()                          # host arrays behind the uploads must outlive the copies
+    counts = eng.download_raw(out, nbins, np.uint64)        # (waits: the host arrays behind the uploads outlive the copies)
     if timings is not None:
         timings.update(bin_ms=ms[0], count_ms=ms[1] + ms[2], count_crowded_ms=ms[2], cells=cells)
     npairs = counts.astype(np.int64).reshape((nr,) if mode == '1d' else (nr, nsub))
@@ -766,10 +708,8 @@ class _CentreSweeps(object):
         self.has_vel = vhost is not None or vcat is not None
         self.reach = float(reach)
         self.cells = cells = pair_cells(L, (self.reach,) * 3, max(n, 1))
-        need, have = profile_device_bytes(n, nh, cells, nr, self.has_vel, hp is not None, hc is not None), eng.free_bytes()
-        if need > have:
-            raise MemoryError("%s: %d particles in %d x %d x %d cells and %d centres take %.2f GiB of work memory, %.2f GiB are free"
-                              % ((who, n) + cells + (nh, need / 2. ** 30, have / 2. ** 30)))
+        eng.need_memory(profile_device_bytes(n, nh, cells, nr, self.has_vel, hp is not None, hc is not None),
+                        "%s: %d particles in %d x %d x %d cells and %d centres take" % ((who, n) + cells + (nh,)))
 
         def pointer(m, host, cat):
             if m == 0:
@@ -818,8 +758,7 @@ class _CentreSweeps(object):
             self._bad(bad)
             if self.timings is not None:
                 self.timings["profile_ms"] = 1e3 * (self.time.perf_counter() - t0)
-            _lib.call("fb_memcpy_d2h", rows.ctypes.data_as(ctypes.c_void_p), out.ptr, rows.nbytes, eng.stream)
-            eng.sync()
+            rows = eng.download_raw(out, rows.shape, np.uint32)
         return rows.astype(np.int64)
 
     def apertures(self, r2):
@@ -841,14 +780,13 @@ class _CentreSweeps(object):
         self._bad(bad)
         if self.timings is not None:
             self.timings["aperture_ms"] = 1e3 * (self.time.perf_counter() - t0)
-        count = np.empty(nh, dtype=np.uint32)
-        _lib.call("fb_memcpy_d2h", count.ctypes.data_as(ctypes.c_void_p), cnt.ptr, count.nbytes, eng.stream)
+        count = eng.download_raw(cnt, nh, np.uint32)
         sigma = None
         if vel:
-            sigma = np.full(nh, np.nan)
             if dev_vel:
-                _lib.call("fb_memcpy_d2h", sigma.ctypes.data_as(ctypes.c_void_p), sg.ptr, sigma.nbytes, eng.stream)
+                sigma = eng.download_raw(sg, nh)
             else:                           # velocities of no particle: every mean is NaN
+                sigma = np.full(nh, np.nan)
                 nanv = np.full((nh, 3), np.nan)
                 _lib.call("fb_memcpy_h2d", vm.ptr, nanv.ctypes.data_as(ctypes.c_void_p), nanv.nbytes, eng.stream)
         eng.sync()

@@ -54,9 +54,7 @@ class GCRInfo(object):
 
     def n_iter_host(self):
         N = self.engine.N
-        h = np.empty((N, N), dtype=np.int32)
-        _lib.call("fb_memcpy_d2h", h.ctypes.data_as(ctypes.c_void_p), self.n_iter.ptr, h.nbytes, self.engine.stream)
-        return h
+        return self.engine.download_raw(self.n_iter, (N, N), np.int32)
 
 
 def _engine_of(d, w, box):
@@ -132,9 +130,7 @@ def _preconditioner(eng, sqrtS, var_dev, var_kind, var_host, w_dev, w_kind, w_ho
         mean = eng._alloc_bytes(N * 8)
         _lib.call("fb_gcr_rhs", eng._plan, w_dev.ptr if w_kind == _PER_VOXEL else var_dev.ptr, w_dev.ptr, w_kind, var_dev.ptr,
                   var_kind, None, _NONE, 0, 0, q.ptr, u.ptr, None, mean.ptr, eng.stream)
-        qbar = np.empty(N)
-        _lib.call("fb_memcpy_d2h", qbar.ctypes.data_as(ctypes.c_void_p), mean.ptr, qbar.nbytes, eng.stream)
-        qbar = np.maximum(qbar, 0.)
+        qbar = np.maximum(eng.download_raw(mean, N), 0.)
     # through eigh: A >= I, so every eigenvalue of P is taken from (0, 1] and P is positive definite whatever cond A
     with _few_blas_threads():
         A = np.eye(N) + (sqrtS * qbar) @ sqrtS
@@ -310,9 +306,7 @@ def _pspec_host(A_re, A_im, w, tau, freqs, decorrelate_amps):
 
 
 def _rows_host(eng, buf, ntau):
-    h = np.empty((eng.N ** 2, ntau))
-    _lib.call("fb_memcpy_d2h", h.ctypes.data_as(ctypes.c_void_p), buf.ptr, h.nbytes, eng.stream)
-    return h
+    return eng.download_raw(buf, (eng.N ** 2, ntau))
 
 
 class LSSAModes(object):

@@ -16,7 +16,7 @@ import numpy as np
 
 from . import _lib
 from . import box as _box
-from .device import FULL, REAL
+from .device import DeviceBuffer, FULL, REAL
 from .sky import _Maps
 
 _ccl = _box._ccl
@@ -127,31 +127,11 @@ def _as_samples(samples):
 
 
 # ---- results ----------------------------------------------------------------------------------------------------------------------
-class DeviceCounts(object):
+class DeviceCounts(DeviceBuffer):
     """The int32 (N, N, N) coverage cube in device memory; ``host()`` copies it out."""
 
     def __init__(self, engine, buf):
-        self.engine, self._buf = engine, buf
-        self.shape = (engine.N,) * 3
-        self.dtype = np.dtype(np.int32)
-        self._host = None
-
-    @property
-    def ptr(self):
-        return self._buf.ptr
-
-    def host(self):
-        if self._host is None:
-            h = np.empty(self.shape, dtype=np.int32)
-            _lib.call("fb_memcpy_d2h", h.ctypes.data_as(ctypes.c_void_p), self.ptr, h.nbytes, self.engine.stream)
-            self.engine.sync()
-            h.setflags(write=False)
-            self._host = h
-        return self._host
-
-    def __array__(self, dtype=None, copy=None):
-        h = self.host()
-        return h if dtype is None else h.astype(dtype)
+        DeviceBuffer.__init__(self, engine, buf, (engine.N,) * 3, np.int32)
 
 
 class UVCoverage(object):
@@ -224,19 +204,13 @@ class Interferometer(object):
         """Distinct samples and their int32 multiplicities: what goes to the device."""
         return collapse_samples(self._samples, self._mult)
 
-    def _need_memory(self, what, nbytes):
-        have = self.box.engine.free_bytes()
-        if nbytes > have:
-            raise MemoryError("%s: a %d^3 box takes %.2f GiB of work memory, %.2f GiB are free"
-                              % (what, self.box.N, nbytes / 2. ** 30, have / 2. ** 30))
-
     def uv_coverage(self):
         """The UVCoverage of this instrument on the box's grid (computed once, kept on the object)."""
         if self._coverage is not None:
             return self._coverage
         eng = self.box.engine
         N = eng.N
-        self._need_memory("uv_coverage", 4 * N ** 3 + eng.nbytes[FULL])
+        eng.need_memory(4 * N ** 3 + eng.nbytes[FULL], "uv_coverage: a %d^3 box takes" % self.box.N)
         samples, mult = self._collapsed()
         sx, sy = channel_scales(self.box, self.redshift)
         du, dv = uv_cell(self.box, self.redshift)
@@ -249,9 +223,7 @@ class Interferometer(object):
         _lib.call("fb_uv_coverage", eng._plan, s_dev.ptr if ns else None, m_dev.ptr if ns else None, ns, sx_dev.ptr, sy_dev.ptr,
                   counts.ptr, 0, eng.stream)
         _lib.call("fb_uv_channel_sums", eng._plan, counts.ptr, sums_dev.ptr, eng.stream)
-        sums = np.empty((2, N), dtype=np.int64)
-        _lib.call("fb_memcpy_d2h", sums.ctypes.data_as(ctypes.c_void_p), sums_dev.ptr, sums.nbytes, eng.stream)
-        eng.sync()
+        sums = eng.download_raw(sums_dev, (2, N), np.int64)
         self._coverage = UVCoverage(counts, sums[0].copy(), sums[1].copy(), du, dv, int(self._mult.sum()))
         return self._coverage
 
@@ -308,7 +280,8 @@ class Interferometer(object):
         channel that is not empty.  A real DeviceArray."""
         self._check_weighting(weighting)
         eng = self.box.engine
-        self._need_memory("psf", (0 if self._coverage is not None else 4 * eng.N ** 3) + eng.nbytes[FULL])
+        eng.need_memory((0 if self._coverage is not None else 4 * eng.N ** 3) + eng.nbytes[FULL],
+                        "psf: a %d^3 box takes" % self.box.N)
         imp = self._zeros()
         ones = np.ones(eng.N, dtype=eng.rdtype)                         # pixel (0, 0) of every channel: the first N values
         _lib.call("fb_memcpy_h2d", imp.ptr, ones.ctypes.data_as(ctypes.c_void_p), ones.nbytes, eng.stream)
@@ -325,7 +298,7 @@ class Interferometer(object):
         sig = self._check_sigma(sigma, weighting)
         box, eng = self.box, self.box.engine
         N = eng.N
-        self._need_memory("noise", (0 if self._coverage is not None else 4 * N ** 3) + eng.nbytes[FULL])
+        eng.need_memory((0 if self._coverage is not None else 4 * N ** 3) + eng.nbytes[FULL], "noise: a %d^3 box takes" % box.N)
         cov = self.uv_coverage()
         if box.rng == "numpy":
             g = eng.upload(np.random.normal(0., 1., (N, N, N)), REAL)
@@ -354,7 +327,7 @@ class Interferometer(object):
         beam = primary_beam.beam_cube() if hasattr(primary_beam, "beam_cube") else primary_beam
         if beam is not None and tuple(np.shape(beam)) != (N, N, N):
             raise ValueError("expected a primary-beam cube of shape %s, got %s" % ((N, N, N), tuple(np.shape(beam))))
-        self._need_memory("observe", (0 if self._coverage is not None else 4 * N ** 3) + eng.nbytes[FULL])
+        eng.need_memory((0 if self._coverage is not None else 4 * N ** 3) + eng.nbytes[FULL], "observe: a %d^3 box takes" % box.N)
         cov = self.uv_coverage()
         field = box._as_real(cube)
         if beam is not None:

@@ -15,7 +15,7 @@ import numpy as np
 
 from . import _lib
 from .device import REAL, DeviceArray
-from .filters import _as_cube, _channel_means, _download, _few_blas_threads
+from .filters import _as_cube, _channel_means, _few_blas_threads
 
 NMAX = 1024
 _PER_CHANNEL, _PER_VOXEL = 0, 1                     # FB_GCR_PER_CHANNEL, FB_GCR_PER_VOXEL
@@ -23,16 +23,6 @@ _X_PLAN = 0                                         # FB_LOS_X_PLAN
 # FB_LOSFIT_*: the status of a line of sight
 OK, TOO_FEW, NONFINITE, NONPOSITIVE, SINGULAR, MAXITER = range(6)
 _SPACES = ("loglog", "semilog", "linear")
-
-
-def _gib(nbytes):
-    return nbytes / 2. ** 30
-
-
-def _need_memory(eng, nbytes, what):
-    free = eng.free_bytes()
-    if nbytes > free:
-        raise MemoryError("%s: %.2f GiB of work memory, %.2f GiB are free" % (what, _gib(nbytes), _gib(free)))
 
 
 def _frequencies(freqs, box, N):
@@ -107,19 +97,13 @@ class LOSFit(object):
         self.order, self.space, self.freqs, self.basis = order, space, freqs, basis
 
     def coeffs_host(self):
-        return _download(self.engine, self.coeffs, (self.order + 1, self.engine.N ** 2))
+        return self.engine.download_raw(self.coeffs, (self.order + 1, self.engine.N ** 2))
 
     def chi2_host(self):
-        return _download(self.engine, self.chi2, (self.engine.N ** 2,))
+        return self.engine.download_raw(self.chi2, (self.engine.N ** 2,))
 
     def status_host(self):
-        return _download_i32(self.engine, self.status)
-
-
-def _download_i32(eng, buf):
-    h = np.empty(eng.N ** 2, dtype=np.int32)
-    _lib.call("fb_memcpy_d2h", h.ctypes.data_as(ctypes.c_void_p), buf.ptr, h.nbytes, eng.stream)
-    return h
+        return self.engine.download_raw(self.status, self.engine.N ** 2, np.int32)
 
 
 def polynomial_filter(field, order=3, space="loglog", freqs=None, weights=None, return_filter=False, box=None):
@@ -153,7 +137,7 @@ def polynomial_filter(field, order=3, space="loglog", freqs=None, weights=None, 
     need = _cube_bytes(eng) * (2 if return_filter else 1) + npix * 4 + (npix * 8 * (order + 2) if return_filter else 0)
     if kind == _PER_VOXEL and not isinstance(weights, DeviceArray):
         need += _cube_bytes(eng)
-    _need_memory(eng, need, "polynomial_filter")
+    eng.need_memory(need, "polynomial_filter:")
     w_dev, w_kind, w_host = _aux(eng, weights, "weights", positive=False)
     basis = legendre_basis(freqs if space == "linear" else np.log(freqs), order)
     pinv_dev = None
@@ -229,7 +213,7 @@ class LSQfitting(object):
         kinds = [_aux_kind(eng, a, what) for a, what in ((sigma, "sigma"), (weights, "weights"))]
         need = _cube_bytes(eng) * (2 if return_filter else 1) + npix * (5 * 8 + 2 * 4 + (8 if beta_guess is not None else 0))
         need += sum(_cube_bytes(eng) for a, k in zip((sigma, weights), kinds) if k == _PER_VOXEL and not isinstance(a, DeviceArray))
-        _need_memory(eng, need, "run_fit")
+        eng.need_memory(need, "run_fit:")
         s_dev, s_kind, _ = _aux(eng, sigma, "sigma", positive=True)
         w_dev, w_kind, _ = _aux(eng, weights, "weights", positive=False)
         tps_dev = None
@@ -253,11 +237,11 @@ class LSQfitting(object):
         _lib.call("fb_los_powerlaw", eng._plan, cube.ptr, _ptr(tps_dev), _ptr(s_dev), s_kind, _ptr(w_dev), w_kind, lnx_dev.ptr, freeind,
                   _ptr(guess_dev), max_iter, tol, resid.ptr, _ptr(model), rows_dev.ptr, n_iter_dev.ptr, status_dev.ptr,
                   ctypes.byref(n_failed), eng.stream)
-        rows = _download(eng, rows_dev, (5, npix))
+        rows = eng.download_raw(rows_dev, (5, npix))
         if not return_filter:
             return resid, rows[0]
-        return resid, rows[0], LSQResult(eng, rows, _download_i32(eng, n_iter_dev), _download_i32(eng, status_dev), model,
-                                         int(n_failed.value))
+        return resid, rows[0], LSQResult(eng, rows, eng.download_raw(n_iter_dev, npix, np.int32),
+                                         eng.download_raw(status_dev, npix, np.int32), model, int(n_failed.value))
 
 
 # ---- 3. Gaussian-process regression --------------------------------------------------------------------------------------------------
@@ -469,13 +453,13 @@ def gpr_filter(field, kernels=None, return_filter=False, opt_messages=True, opt_
         kernels = list(kernels)
         if not kernels or not all(isinstance(k, GPRKernel) for k in kernels):
             raise TypeError("kernels: a list of GPRKernel")
-    _need_memory(eng, N ** 3 * 8 + _cube_bytes(eng) + (N * N + 2 * N) * 8, "gpr_filter")
+    eng.need_memory(N ** 3 * 8 + _cube_bytes(eng) + (N * N + 2 * N) * 8, "gpr_filter:")
     t0 = time.perf_counter()
     mean_dev = _channel_means(eng, cube)
     cov_dev = eng._alloc_bytes(N * N * 8)
     _lib.call("fb_channel_covariance", eng._plan, cube.ptr, mean_dev.ptr, cov_dev.ptr, eng.stream)
-    mean = _download(eng, mean_dev, (N,))
-    gram = _download(eng, cov_dev, (N, N)) * (npix - 1.)           # x^T x
+    mean = eng.download_raw(mean_dev, (N,))
+    gram = eng.download_raw(cov_dev, (N, N)) * (npix - 1.)           # x^T x
     gram = 0.5 * (gram + gram.T)
     t1 = time.perf_counter()
     var = float(np.trace(gram)) / (float(npix) * N)                # np.var(x): every channel of x has zero mean

@@ -190,13 +190,6 @@ def _check_nu(nu):
     return nu
 
 
-def _download(eng, buf, n):
-    h = np.empty(n, dtype=np.float64)
-    _lib.call("fb_memcpy_d2h", h.ctypes.data_as(ctypes.c_void_p), buf.ptr, h.nbytes, eng.stream)
-    eng.sync()
-    return h
-
-
 def field_moments(cube, per_channel=False):
     """(mean, sigma) of a real device cube, sigma the population standard deviation: two ``sum_real`` reductions for the box, or
     per channel (arrays of N) fb_channel_means and fb_channel_moments about those means."""
@@ -210,7 +203,7 @@ def field_moments(cube, per_channel=False):
     mom_dev = eng._alloc_bytes(2 * N * 8)
     _lib.call("fb_channel_means", eng._plan, cube.ptr, mean_dev.ptr, eng.stream)
     _lib.call("fb_channel_moments", eng._plan, cube.ptr, mean_dev.ptr, mom_dev.ptr, eng.stream)
-    mean, mom = _download(eng, mean_dev, N), _download(eng, mom_dev, 2 * N).reshape(2, N)
+    mean, mom = eng.download_raw(mean_dev, N), eng.download_raw(mom_dev, (2, N))
     npix = float(N) ** 2
     d = mom[0] / npix                               # what rounding left of the mean
     return mean + d, np.sqrt(np.maximum(mom[1] / npix - d * d, 0.))

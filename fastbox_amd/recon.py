@@ -16,41 +16,18 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .device import DeviceArray, HALF, REAL
+from .device import DeviceArray, DeviceBuffer, HALF, REAL
 from .halos import HaloCatalogue, WINDOWS, _next_realisation, pair_counts
 
 CONVENTIONS = ("sym", "iso")
 N_MAX = 2 ** 31 - 2
 
 
-class DeviceValues(object):
+class DeviceValues(DeviceBuffer):
     """fp64 values per particle on the device, shape (n,) or (n, k); ``np.asarray(v)`` is the host copy."""
 
-    dtype = np.dtype(np.float64)
-
     def __init__(self, engine, buf, shape):
-        self.engine, self._buf, self.shape = engine, buf, tuple(int(s) for s in shape)
-        self._host = None
-
-    @property
-    def ptr(self):
-        return self._buf.ptr if self._buf is not None else None
-
-    def __len__(self):
-        return self.shape[0]
-
-    def host(self):
-        if self._host is None:
-            h = np.empty(self.shape, dtype=np.float64)
-            if h.size:
-                _lib.call("fb_memcpy_d2h", h.ctypes.data_as(ctypes.c_void_p), self.ptr, h.nbytes, self.engine.stream)
-            h.setflags(write=False)
-            self._host = h
-        return self._host
-
-    def __array__(self, dtype=None, copy=None):
-        h = self.host()
-        return h if dtype is None or np.dtype(dtype) == h.dtype else h.astype(dtype)
+        DeviceBuffer.__init__(self, engine, buf, shape, np.float64)
 
     def __repr__(self):
         return "DeviceValues(shape=%s)" % (self.shape,)
@@ -307,10 +284,8 @@ def reconstruct(box, data, randoms=None, smoothing=10., bias=1., f=0., conventio
         nr, rptr = _positions(box, randoms, "randoms", keep)
     if not 1 <= nr <= N_MAX:
         raise ValueError("randoms: between 1 and 2^31 - 2 particles")
-    need, have = int(eng.lib.fb_recon_work_bytes(eng._plan, nd, nr)), eng.free_bytes()
-    if need > have:
-        raise MemoryError("reconstruct: %d data and %d randoms on a %d^3 grid take %.2f GiB of work memory, %.2f GiB are free"
-                          % (nd, nr, N, need / 2. ** 30, have / 2. ** 30))
+    eng.need_memory(int(eng.lib.fb_recon_work_bytes(eng._plan, nd, nr)),
+                    "reconstruct: %d data and %d randoms on a %d^3 grid take" % (nd, nr, N))
     own = None                          # randoms made here are shifted in place
     if grid or drawn:
         own = grid_catalogue_nodes(box) if grid else uniform_catalogue(box, nr, seed=seed, realisation=0)

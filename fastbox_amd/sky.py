@@ -10,8 +10,6 @@ Random numbers follow the box: ``rng='numpy'`` draws the reference's legacy glob
 host in the reference's order (same seed => same maps / cube), ``rng='device'`` uses the counter
 generator (streams 2-4).
 """
-import ctypes
-
 import numpy as np
 
 from . import _lib
@@ -53,9 +51,7 @@ class _Maps(object):
         return self.eng._alloc_bytes(self.N * self.N * item)
 
     def download(self, buf):
-        h = np.empty((self.N, self.N), dtype=self.eng.rdtype)
-        _lib.call("fb_memcpy_d2h", h.ctypes.data_as(ctypes.c_void_p), buf.ptr, h.nbytes, self.eng.stream)
-        return h.astype(np.float64)
+        return self.eng.download_raw(buf, (self.N, self.N), self.eng.rdtype).astype(np.float64)
 
     def smooth(self, buf, sigma_pix):
         w, radius = _gaussian_weights(sigma_pix)

@@ -20,7 +20,7 @@ import time
 import numpy as np
 
 from . import _lib
-from .device import DeviceArray, REAL
+from .device import DeviceArray, DeviceBuffer, REAL
 
 MASK_ALL, MASK_THRESHOLD, MASK_U8, MASK_FIELD = 0, 1, 2, 3        # FB_VOID_MASK_*
 NCOL = 11                                                           # columns of fb_region_stats
@@ -29,30 +29,13 @@ MAX_LABEL = 2 ** 30
 MAX_WATERSHED_N = 1290                                              # N^3 < 2^31: bit 31 of a parent word marks a root
 
 
-class VoidLabels(object):
+class VoidLabels(DeviceBuffer):
     """Region labels on the device: int32 [N][N][N] in C order, 0 = outside the mask, 1..n_labels.  ``np.asarray(labels)`` is
     the (N, N, N) int32 host copy."""
 
     def __init__(self, engine, buf, n_labels):
-        self.engine, self._buf, self.n_labels = engine, buf, int(n_labels)
-        self._host = None
-        self.shape = (engine.N,) * 3
-
-    @property
-    def ptr(self):
-        return self._buf.ptr
-
-    def host(self):
-        if self._host is None:
-            h = np.empty(self.shape, dtype=np.int32)
-            _lib.call("fb_memcpy_d2h", h.ctypes.data_as(ctypes.c_void_p), self.ptr, h.nbytes, self.engine.stream)
-            h.setflags(write=False)
-            self._host = h
-        return self._host
-
-    def __array__(self, dtype=None, copy=None):
-        h = self.host()
-        return h if dtype is None or np.dtype(dtype) == h.dtype else h.astype(dtype)
+        DeviceBuffer.__init__(self, engine, buf, (engine.N,) * 3, np.int32)
+        self.n_labels = int(n_labels)
 
     def __repr__(self):
         return "VoidLabels(%d regions, N=%d)" % (self.n_labels, self.engine.N)
@@ -246,9 +229,7 @@ def region_statistics(labels, field=None, box=None):
         raise ValueError("void_labels: labels outside 0 .. %d" % lab.n_labels)
     if bad.value & 1:
         raise ValueError("field: not finite in a voxel of a region (label >= 1)")
-    raw = np.empty(NCOL * n1, dtype=np.float64)
-    _lib.call("fb_memcpy_d2h", raw.ctypes.data_as(ctypes.c_void_p), dev.ptr, raw.nbytes, eng.stream)
-    return RegionStats(lab, raw, dev)
+    return RegionStats(lab, eng.download_raw(dev, NCOL * n1), dev)
 
 
 def merge_regions(labels, field, merge_threshold, box=None):
@@ -362,11 +343,8 @@ def stack_voids_at(void_cat, void_labels, box, field, centres, radii, grid_scale
     mean_d, cnt_d, hit_d = eng._alloc_bytes(8 * P), eng._alloc_bytes(8 * P), eng._alloc_bytes(4 * max(nv, 1))
     _lib.call("fb_stack_voids", eng._plan, lab.ptr, f.ptr, vbuf.ptr if nv else None, cbuf.ptr if nv else None, nv, axes,
               gbuf.ptr, grid_pix, mean_d.ptr, cnt_d.ptr, hit_d.ptr, eng.stream)
-    mean = np.empty(P)
-    cnt = np.empty(P, dtype=np.int64)
-    hit = np.zeros(max(nv, 1), dtype=np.int32)
-    for h, d in ((mean, mean_d), (cnt, cnt_d), (hit, hit_d)):
-        _lib.call("fb_memcpy_d2h", h.ctypes.data_as(ctypes.c_void_p), d.ptr, h.nbytes, eng.stream)
+    mean, cnt = eng.download_raw(mean_d, P), eng.download_raw(cnt_d, P, np.int64)
+    hit = eng.download_raw(hit_d, max(nv, 1), np.int32)
     shape = (grid_pix,) * 3
     stacked = np.ma.array(mean.reshape(shape), mask=(cnt == 0).reshape(shape))
     failures = [x for x, h in zip(c.tolist(), hit[:nv]) if not h]

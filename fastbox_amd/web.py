@@ -20,7 +20,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .device import DeviceArray, FULL, HALF, REAL
+from .device import DeviceArray, DeviceBuffer, FULL, HALF, REAL
 
 NT_MAX = 16                              # FB_WEB_NT_MAX of the library
 COMPONENTS = ("xx", "yy", "zz", "xy", "xz", "yz")
@@ -75,13 +75,6 @@ def web_device_bytes(N, precision="f32", kind="tidal", from_spectrum=False, eige
     return max(tensor, 6 * real + cls)
 
 
-def _check_memory(eng, need, what):
-    have = eng.free_bytes()
-    if need > have:
-        raise MemoryError("%s: a %d^3 grid takes %.2f GiB of work memory, %.2f GiB are free"
-                          % (what, eng.N, need / 2. ** 30, have / 2. ** 30))
-
-
 # ---------------------------------------------------------------------- results
 class TensorField(object):
     """A symmetric tensor field of a box on the device: six real DeviceArrays ``xx``, ``yy``, ``zz``, ``xy``, ``xz``, ``yz``
@@ -103,34 +96,12 @@ class TensorField(object):
         return "TensorField(kind=%s, N = %d, smoothing = %g Mpc)" % (self.kind, self.engine.N, self.smoothing)
 
 
-class ClassCube(object):
+class ClassCube(DeviceBuffer):
     """The classes of every voxel on the device, uint8 (N, N, N): 0 void, 1 sheet, 2 filament, 3 knot, 255 where the tensor is
     not finite.  ``host()`` / ``np.asarray`` give the host copy."""
 
-    dtype = np.dtype(np.uint8)
-
     def __init__(self, engine, buf):
-        self.engine, self._buf = engine, buf
-        N = engine.N
-        self.shape = (N, N, N)
-        self._host = None
-
-    @property
-    def ptr(self):
-        return self._buf.ptr
-
-    def host(self):
-        if self._host is None:
-            h = np.empty(self.shape, dtype=np.uint8)
-            _lib.call("fb_memcpy_d2h", h.ctypes.data_as(ctypes.c_void_p), self.ptr, h.nbytes, self.engine.stream)
-            self.engine.sync()
-            h.setflags(write=False)
-            self._host = h
-        return self._host
-
-    def __array__(self, dtype=None, copy=None):
-        h = self.host()
-        return h if dtype is None or np.dtype(dtype) == h.dtype else h.astype(dtype)
+        DeviceBuffer.__init__(self, engine, buf, (engine.N,) * 3, np.uint8)
 
     def __repr__(self):
         return "ClassCube(shape=%s)" % (self.shape,)
@@ -164,7 +135,7 @@ class CosmicWeb(object):
         c = class_index(kind)
         if self.classes is None:
             raise ValueError("mask: classes were not kept (a scalar threshold and return_classes=True)")
-        _check_memory(self.engine, self.engine.nbytes[REAL], "mask")
+        self.engine.need_memory(self.engine.nbytes[REAL], "mask: a %d^3 grid takes" % self.N)
         out = self.engine.empty(REAL)
         _lib.call("fb_web_mask", self.engine._plan, self.classes.ptr, c, out.ptr, self.engine.stream)
         return out
@@ -239,7 +210,8 @@ def tensor_field(box, components, kind=None, smoothing=0.):
     if len(components) != 6:
         raise ValueError("components: six real fields (xx, yy, zz, xy, xz, yz)")
     checked = [_check_real(eng, c, "components") for c in components]
-    _check_memory(eng, sum(eng.nbytes[REAL] for c in checked if not isinstance(c, DeviceArray)), "tensor_field")
+    eng.need_memory(sum(eng.nbytes[REAL] for c in checked if not isinstance(c, DeviceArray)),
+                    "tensor_field: a %d^3 grid takes" % eng.N)
     out = TensorField(eng, [_device(eng, c) for c in checked], kind, smoothing)
     eng.sync()                          # host arrays behind the uploads must outlive the copies
     return out
@@ -270,8 +242,9 @@ def tidal_tensor(box, delta_x=None, delta_k=None, smoothing=0.):
             if delta_x is None:
                 raise ValueError("no delta_x: realise_density() first, or pass delta_x or delta_k")
         src = _check_real(eng, delta_x, "delta_x")
-    _check_memory(eng, web_device_bytes(eng.N, eng.precision, "tidal", stage="tensor")
-                  + (eng.nbytes[FULL] if delta_k is not None and not isinstance(delta_k, DeviceArray) else 0), "tidal_tensor")
+    eng.need_memory(web_device_bytes(eng.N, eng.precision, "tidal", stage="tensor")
+                    + (eng.nbytes[FULL] if delta_k is not None and not isinstance(delta_k, DeviceArray) else 0),
+                    "tidal_tensor: a %d^3 grid takes" % eng.N)
     if src is not None:
         half = eng.fft_r2c(_device(eng, src))
     else:
@@ -303,8 +276,8 @@ def shear_tensor(box, velocity, smoothing=0., H0=None):
     if len(vel) != 3:
         raise ValueError("velocity: three real fields (v_x, v_y, v_z)")
     vel = [_check_real(eng, v, "velocity") for v in vel]
-    _check_memory(eng, web_device_bytes(eng.N, eng.precision, "shear", stage="tensor")
-                  + sum(eng.nbytes[REAL] for v in vel if not isinstance(v, DeviceArray)), "shear_tensor")
+    eng.need_memory(web_device_bytes(eng.N, eng.precision, "shear", stage="tensor")
+                    + sum(eng.nbytes[REAL] for v in vel if not isinstance(v, DeviceArray)), "shear_tensor: a %d^3 grid takes" % eng.N)
     vk = [eng.fft_r2c(_device(eng, v)) for v in vel]
     spectra = [eng.empty(HALF) for _ in range(6)]
     _lib.call("fb_shear_k", eng._plan, _ptrs(vk), _ptrs(spectra), R, H0, eng.stream)
@@ -342,8 +315,9 @@ def eigenvalues(tensor):
     cyclic Jacobi in fp64 on both precisions, the error of the order of 2^-53 ||A||_F whatever the spectrum; NaN where a
     component is not finite."""
     tensor = _tensor(tensor)
-    _check_memory(tensor.engine, web_device_bytes(tensor.engine.N, tensor.engine.precision, eigenvalues=True, classes=False,
-                                                  stage="classify"), "eigenvalues")
+    eng = tensor.engine
+    eng.need_memory(web_device_bytes(eng.N, eng.precision, eigenvalues=True, classes=False, stage="classify"),
+                    "eigenvalues: a %d^3 grid takes" % eng.N)
     return tuple(_eigen(tensor, None, -1, None, True, False, False)[0])
 
 
@@ -359,8 +333,8 @@ def classify(tensor, threshold=0., weight=None, return_classes=True, return_eige
     t, scalar = _check_thresholds(threshold)
     w = _check_real(eng, weight, "weight") if weight is not None else None
     keep = bool(return_classes) and scalar
-    _check_memory(eng, web_device_bytes(eng.N, eng.precision, eigenvalues=bool(return_eigenvalues), classes=keep, stage="classify")
-                  + (eng.nbytes[REAL] if w is not None and not isinstance(w, DeviceArray) else 0), "classify")
+    eng.need_memory(web_device_bytes(eng.N, eng.precision, eigenvalues=bool(return_eigenvalues), classes=keep, stage="classify")
+                    + (eng.nbytes[REAL] if w is not None and not isinstance(w, DeviceArray) else 0), "classify: a %d^3 grid takes" % eng.N)
     wd = _device(eng, w) if w is not None else None
     eig, classes, counts, wsum, n_nan = _eigen(tensor, t, 0, wd, bool(return_eigenvalues), keep, True)
     return CosmicWeb(eng, t, counts, n_nan, wsum, classes, tuple(eig) if eig is not None else None)
