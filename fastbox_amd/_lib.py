@@ -120,6 +120,9 @@ SIGNATURES = {
     "fb_halo_profiles": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, P_double, c_int, c_void_p, P_i32, c_void_p]),
     "fb_halo_apertures": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_i64, c_double, c_void_p, c_void_p, c_void_p, c_void_p,
                                   P_i32, c_void_p]),
+    "fb_triplet_work_bytes": (c_i64, [c_i64, c_i64, c_int, c_int, c_int]),
+    "fb_triplet_multipoles": (c_int, [c_void_p, c_void_p, c_void_p, c_i64, P_i32, P_double, c_int, c_int, c_void_p, c_i64, c_void_p,
+                                      c_void_p, P_i32, c_int, c_void_p, P_i32, P_double, c_void_p]),
     "fb_real_axpby": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_double, c_double, c_double, c_void_p]),
     "fb_real_multiply": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "fb_real_to_complex": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p]),

@@ -1194,6 +1194,28 @@ class CosmoBox(object):
         from . import halos
         return halos.spherical_overdensity(self, centres, particles, **kw)
 
+    def triplet_multipoles(self, positions, edges, lmax=10, weights=None, probe=None, timings=None):
+        """Additive: the raw three-point multipole moments M_l(b1, b2) of a weighted catalogue, its pair counts and, with
+        ``probe``, the harmonic coefficients a_lm of chosen primaries, summed on the device.  Keywords and definition:
+        ``fastbox_amd.halos.triplet_multipoles``; DESIGN.md section 4."""
+        from . import halos
+        return halos.triplet_multipoles(self, positions, edges, lmax=lmax, weights=weights, probe=probe, timings=timings)
+
+    def three_point(self, data, edges, lmax=10, randoms=None, weights=None, seed=None):
+        """Additive: the multipoles zeta_l(r1, r2), l <= ``lmax`` <= 10, of the configuration-space three-point correlation
+        function of a catalogue in this periodic box -- what nbodykit's ``SimulationBox3PCF`` gives on the host -- by the
+        algorithm of Slepian & Eisenstein (2015) on the device, O(n x neighbours).  ``data``: a ``ColaParticles``,
+        ``FoFHalos``, ``SOHalos`` or other HaloCatalogue of this box, or a host (n, 3) array; ``weights``: n host values
+        (default 1); ``edges``: up to 32 radial bins in Mpc, edges[0] > 0, the last edge below min(L) / 2.  ``randoms`` None:
+        zeta = (2 l + 1) M_l / norm - [l = 0], the multipoles of the full three-point function; a number: that many uniform
+        points per datum drawn on the device (``uniform_catalogue`` with ``seed``), or a catalogue / (n, 3) array: the randoms
+        join the sweep with weight -W_d / n_r each and zeta = (2 l + 1) M_l / norm is the connected zeta_l of N = D - R
+        (Szapudi & Szalay).  Data and randoms are joined on the device.  Returns a ``fastbox_amd.halos.ThreePoint``.
+        Definition, normalisation and what is out of scope: DESIGN.md section 4.  Agreement with nbodykit is intended, not
+        verified."""
+        from . import halos
+        return halos.three_point(self, data, edges, lmax=lmax, randoms=randoms, weights=weights, seed=seed)
+
     # ------------------------------------------------------------ density-field reconstruction and mesh readout
     def reconstruct(self, data, randoms=None, smoothing=10., bias=1., f=0., convention='sym', window='cic', delta=None,
                     seed=None, return_displacement=False):

@@ -874,6 +874,202 @@ def spherical_overdensity(box, centres, particles, delta=200., reference='mean',
     return SOHalos(eng, sw.cbuf, nh, radius, mass, status, count, HaloCatalogue(eng, com, nh), vel, sigma, prof, delta, rho_ref)
 
 
+# ---------------------------------------------------------------------- three-point correlation multipoles
+TRIPLET_MAX_NR, TRIPLET_MAX_L, TRIPLET_MAX_PROBE = 32, 10, 64       # FB_TRIP_MAX_NR, _MAX_L, _MAX_PROBE of fb_triplets.hip
+
+
+def triplet_edges(L, edges, lmax=10):
+    """The checked radial edges and order of ``triplet_multipoles``: strictly ascending, finite, edges[0] > 0, at most 32 bins,
+    the last edge below min(L) / 2; lmax an integer from 0 to 10.  ValueError otherwise."""
+    e = np.array(edges, dtype=np.float64)
+    if e.ndim != 1 or e.size < 2 or not np.all(np.isfinite(e)) or not e[0] > 0. or not np.all(e[1:] > e[:-1]):
+        raise ValueError("edges: a strictly ascending array of at least 2 finite values, edges[0] > 0")
+    if e.size - 1 > TRIPLET_MAX_NR:
+        raise ValueError("edges: at most %d bins, got %d" % (TRIPLET_MAX_NR, e.size - 1))
+    if not e[-1] < 0.5 * min(L):
+        raise ValueError("edges: the last edge %.6g Mpc must be below half the shortest box side (%.6g Mpc)" % (e[-1], 0.5 * min(L)))
+    if isinstance(lmax, bool) or int(lmax) != lmax or not 0 <= int(lmax) <= TRIPLET_MAX_L:
+        raise ValueError("lmax: an integer from 0 to %d" % TRIPLET_MAX_L)
+    return e, int(lmax)
+
+
+def triplet_fx_bits(n, wmax=1.):
+    """(F_a, F_S, F_M): the fractional bits of the device's fixed-point sums of a_lm, S and M for n particles of largest
+    |weight| wmax: 93 - e with bound < 2^e (frexp), the bounds being 2 n wmax, n wmax^2 and 4 (n wmax)^3."""
+    def bits(bound):
+        return 93 - (int(np.frexp(bound)[1]) if bound > 0. else 0)
+    nw = float(n) * float(wmax)
+    return bits(2. * nw), bits(float(n) * float(wmax) * float(wmax)), bits(4. * nw * nw * nw)
+
+
+def triplet_device_bytes(n, cells, nr=TRIPLET_MAX_NR, lmax=TRIPLET_MAX_L, weighted=False, host_positions=False, nprobe=0):
+    """Device bytes triplet_multipoles allocates beside the catalogue: the work buffer (32 bytes a particle -- the permuted
+    positions, cell ids and permutation --, 8 more with weights, and the workgroups' partial sums), the outputs, and the
+    uploads of host positions and weights."""
+    ncells = int(cells[0]) * int(cells[1]) * int(cells[2])
+    need = int(_lib.load().fb_triplet_work_bytes(int(n), ncells, int(nr), int(lmax), 1 if weighted else 0))
+    need += 8 * (lmax + 1) * nr * nr + 8 * nr + 8 * nprobe * (lmax + 1) ** 2 * nr + 512
+    return need + (24 * n + 32 if host_positions else 0) + (8 * n + 32 if weighted else 0)
+
+
+def three_point_normalisation(edges, L, W_d):
+    """(volumes, norm) of ``three_point``, pure numpy: V_b = 4 pi / 3 (e_(b+1)^3 - e_b^3) and norm(b1, b2) = W_d^3 / V^2
+    V_b1 V_b2, V = Lx Ly Lz: the expected weighted triplet count of an unclustered catalogue of total weight W_d."""
+    e = np.asarray(edges, dtype=np.float64)
+    vol = (4. * np.pi / 3.) * (e[1:] ** 3 - e[:-1] ** 3)
+    V = float(L[0]) * float(L[1]) * float(L[2])
+    return vol, float(W_d) ** 3 / V ** 2 * vol[:, None] * vol[None, :]
+
+
+def triplet_multipoles(box, positions, edges, lmax=10, weights=None, probe=None, timings=None):
+    """The raw three-point multipole moments of a weighted catalogue in the periodic box, summed on the device (Slepian &
+    Eisenstein 2015; definition and design in DESIGN.md section 4): per primary i and radial bin b the harmonic coefficients
+    a_lm(b) = sum_j w_j Y_lm(u_ij) of its neighbours, then M_l(b1, b2) = sum_i w_i ((4 pi / (2 l + 1)) sum_m a_lm(b1) a_lm(b2) -
+    [b1 = b2] sum_j w_j^2), which is the sum over ordered triplets (i; j != k) of w_i w_j w_k P_l(u_ij . u_ik).  ``positions``:
+    a HaloCatalogue of this box or a host (n, 3) array in Mpc, periodic and wrapped on read; ``weights``: n host values of any
+    sign (default 1); ``edges``: radial edges in Mpc, edges[0] > 0, lower edge inclusive, upper exclusive, decided on squares
+    (``triplet_edges``); ``probe``: up to 64 indices into ``positions`` whose a_lm are returned as well; ``timings``: a dict that
+    receives the milliseconds of the stages.  Returns (M float64 (lmax + 1, nr, nr), npairs int64 (nr,): the ordered pairs of
+    ``pair_counts``, alm float64 (nprobe, (lmax + 1)^2, nr) -- index l^2 + l + m -- or None).  The sums are fixed-point: the same
+    bit for bit from call to call and for any order of the particles.  ValueError: bad arguments, a host position or weight
+    that is not finite (all before the device is touched), a device position that is not finite or too large to wrap into
+    the box; MemoryError before any allocation if the work memory does not fit."""
+    eng = box.engine
+    L = (float(box.Lx), float(box.Ly), float(box.Lz))
+    e, lmax = triplet_edges(L, edges, lmax)
+    nr = e.size - 1
+    n, hp, cat = _pair_positions(eng, positions, "positions")
+    if n > 2 ** 31 - 2:
+        raise ValueError("triplet_multipoles: at most 2^31 - 2 particles")
+    if hp is not None and not np.all(np.isfinite(hp)):
+        raise ValueError("positions: a position is not finite")
+    w = None
+    if weights is not None:
+        w = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+        if w.size != n:
+            raise ValueError("weights: expected %d values, got %d" % (n, w.size))
+        if not np.all(np.isfinite(w)):
+            raise ValueError("weights: a weight is not finite")
+    pr = np.zeros(0, dtype=np.int32)
+    if probe is not None:
+        pq = np.asarray(probe).reshape(-1)
+        if pq.size > TRIPLET_MAX_PROBE or (pq.size and (np.any(pq != np.floor(pq)) or pq.min() < 0 or pq.max() >= n)):
+            raise ValueError("probe: at most %d indices into the %d positions" % (TRIPLET_MAX_PROBE, n))
+        pr = np.ascontiguousarray(pq, dtype=np.int32)
+    nlm = (lmax + 1) ** 2
+    cells = pair_cells(L, (e[-1],) * 3, max(n, 1))
+    eng.need_memory(triplet_device_bytes(n, cells, nr, lmax, w is not None, hp is not None, pr.size),
+                    "triplet_multipoles: %d particles in %d x %d x %d cells take" % ((n,) + cells))
+    keep = []
+    pptr = wptr = None
+    if n:
+        if cat is not None:
+            pptr = cat.ptr
+        else:
+            keep.append(eng.upload_raw(hp))
+            pptr = keep[-1].ptr
+        if w is not None:
+            keep.append(eng.upload_raw(w))
+            wptr = keep[-1].ptr
+    wbytes = int(eng.lib.fb_triplet_work_bytes(n, cells[0] * cells[1] * cells[2], nr, lmax, 1 if w is not None else 0))
+    work, mout, pout = eng._alloc_bytes(wbytes), eng._alloc_bytes(8 * (lmax + 1) * nr * nr), eng._alloc_bytes(8 * nr)
+    aout = eng._alloc_bytes(8 * pr.size * nlm * nr) if pr.size else None
+    e2 = np.ascontiguousarray(e * e)
+    bad = ctypes.c_int32(0)
+    ms = (ctypes.c_double * 3)()
+    _lib.call("fb_triplet_multipoles", eng._plan, pptr, wptr, n, (ctypes.c_int32 * 3)(*cells),
+              e2.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), nr, lmax, work.ptr, wbytes, mout.ptr, pout.ptr,
+              pr.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)) if pr.size else None, int(pr.size), aout.ptr if pr.size else None,
+              ctypes.byref(bad), ms if timings is not None else None, eng.stream)
+    if bad.value & 1:
+        raise ValueError("triplet_multipoles: a position is not finite, or too large to wrap into the box")
+    if bad.value:
+        raise ValueError("triplet_multipoles: a weight is not finite, or (n max |w|)^3 overflows")
+    M = eng.download_raw(mout, (lmax + 1, nr, nr))
+    npairs = eng.download_raw(pout, nr, np.uint64).astype(np.int64)
+    alm = eng.download_raw(aout, (pr.size, nlm, nr)) if pr.size else None
+    if timings is not None:
+        timings.update(bin_ms=ms[0], sweep_ms=ms[1], finish_ms=ms[2], cells=cells)
+    return M, npairs, alm
+
+
+class ThreePoint(object):
+    """The three-point correlation multipoles of ``three_point`` (DESIGN.md section 4).  Members: ``edges`` (nr + 1, Mpc);
+    ``r``, the arithmetic bin midpoints; ``volumes`` V_b = 4 pi / 3 (e_(b+1)^3 - e_b^3); ``lmax``; ``multipoles`` (lmax + 1,
+    nr, nr): the raw moments M_l(b1, b2) of ``triplet_multipoles``; ``npairs`` int64 (nr,): the ordered pairs of the sweep's
+    catalogue; ``zeta`` (lmax + 1, nr, nr) = (2 l + 1) M_l / norm, norm = W_d^3 / V^2 V_b1 V_b2 (``three_point_normalisation``),
+    minus 1 at l = 0 without randoms; ``connected``: True with randoms (zeta is the connected zeta_l(r1, r2) of the D - R
+    field), False without (the multipoles of the full three-point function, xi(r1) + xi(r2) + xi(r3) included); ``n_data``,
+    ``n_random``; ``catalogue`` and ``weights``: what the sweep ran on (data then randoms, joined on the device; None
+    weights: all 1)."""
+
+    def __init__(self, edges, L, lmax, M, npairs, W_d, connected, n_data, n_random, catalogue=None, weights=None):
+        self.edges = np.array(edges, dtype=np.float64)
+        self.r = 0.5 * (self.edges[1:] + self.edges[:-1])
+        self.lmax, self.connected, self.n_data, self.n_random = int(lmax), bool(connected), int(n_data), int(n_random)
+        self.multipoles, self.npairs = np.array(M, dtype=np.float64), np.array(npairs, dtype=np.int64)
+        self.catalogue, self.weights = catalogue, weights
+        self.volumes, norm = three_point_normalisation(self.edges, L, W_d)
+        with np.errstate(divide='ignore', invalid='ignore'):
+            self.zeta = (2. * np.arange(self.lmax + 1) + 1.)[:, None, None] * self.multipoles / norm[None, :, :]
+        if not self.connected:
+            self.zeta[0] -= 1.
+
+    def __repr__(self):
+        return "ThreePoint(lmax=%d, %d bins, %d data, %d randoms, %s)" % (self.lmax, self.edges.size - 1, self.n_data, self.n_random,
+                                                                          "connected" if self.connected else "full")
+
+
+def three_point(box, data, edges, lmax=10, randoms=None, weights=None, seed=None):
+    """CosmoBox.three_point: see there."""
+    from . import recon
+    eng = box.engine
+    L = (float(box.Lx), float(box.Ly), float(box.Lz))
+    e, lmax = triplet_edges(L, edges, lmax)
+    nd, hd, cd = _pair_positions(eng, data, "data")
+    if hd is not None and not np.all(np.isfinite(hd)):
+        raise ValueError("data: a position is not finite")
+    wd = None
+    if weights is not None:
+        wd = np.ascontiguousarray(np.asarray(weights, dtype=np.float64).reshape(-1))
+        if wd.size != nd or not np.all(np.isfinite(wd)):
+            raise ValueError("weights: %d finite values" % nd)
+    W_d = float(np.sum(wd)) if wd is not None else float(nd)
+    if randoms is None:
+        M, npairs, _ = triplet_multipoles(box, data, e, lmax, weights=wd)
+        return ThreePoint(e, L, lmax, M, npairs, W_d, False, nd, 0, data if cd is not None else None, wd)
+    if isinstance(randoms, HaloCatalogue) or np.ndim(randoms) == 2:
+        nrn, hr, cr = _pair_positions(eng, randoms, "randoms")
+        if hr is not None and not np.all(np.isfinite(hr)):
+            raise ValueError("randoms: a position is not finite")
+    else:
+        if isinstance(randoms, bool) or np.ndim(randoms) != 0 or not np.isfinite(randoms) or randoms <= 0:
+            raise ValueError("randoms: None, a positive number per datum, or a catalogue")
+        nrn, hr = int(round(float(randoms) * nd)), None
+        if nrn > 2 ** 31 - 2 - nd:
+            raise ValueError("three_point: at most 2^31 - 2 particles, data and randoms together")
+        cr = recon.uniform_catalogue(box, nrn, seed=seed) if nrn else None
+    if nd + nrn > 2 ** 31 - 2:
+        raise ValueError("three_point: at most 2^31 - 2 particles, data and randoms together")
+    if nd == 0 or nrn == 0:
+        raise ValueError("three_point: randoms need at least one datum and one random point")
+    cells = pair_cells(L, (e[-1],) * 3, nd + nrn)
+    eng.need_memory(triplet_device_bytes(nd + nrn, cells, e.size - 1, lmax, True) + 24 * (nd + nrn),
+                    "three_point: %d data and %d randoms in %d x %d x %d cells take" % ((nd, nrn) + cells))
+    # data then randoms in one buffer on the device; the randoms weigh -W_d / n_r each (Szapudi & Szalay: N = D - R)
+    joined = eng._alloc_bytes(24 * (nd + nrn))
+    for off, m, host, cat in ((0, nd, hd, cd), (24 * nd, nrn, hr, cr)):
+        if cat is not None:
+            _lib.call("fb_memcpy_d2d", joined.ptr + off, cat.ptr, 24 * m, eng.stream)
+        else:
+            _lib.call("fb_memcpy_h2d", joined.ptr + off, host.ctypes.data_as(ctypes.c_void_p), 24 * m, eng.stream)
+    eng.sync()                          # host arrays behind the uploads must outlive the copies
+    w = np.concatenate([wd if wd is not None else np.ones(nd), np.full(nrn, -W_d / nrn)])
+    cat = HaloCatalogue(eng, joined, nd + nrn)
+    M, npairs, _ = triplet_multipoles(box, cat, e, lmax, weights=w)
+    return ThreePoint(e, L, lmax, M, npairs, W_d, True, nd, nrn, cat, w)
+
+
 def paint(box, positions, weights=None, window='cic', compensated=False):
     """CosmoBox.paint_catalogue: see there."""
     eng, N = box.engine, box.N

@@ -515,6 +515,41 @@ int fb_halo_profiles(fb_plan* plan, void* work, const double* centres, int64_t n
 int fb_halo_apertures(fb_plan* plan, void* work, const double* centres, const double* r2, int64_t nh, double reach,
                       uint32_t* count_out, double* com_out, double* vmean_out, double* sigma_out, int* bad, void* stream);
 
+/* ---- three-point correlation multipoles of a catalogue (nbodykit's SimulationBox3PCF) -----------------
+ * One box on one GPU; particle data are fp64 whatever the plan's precision.  pos: DEVICE double[n][3] in Mpc, periodic in the
+ * plan's box, wrapped on read; w: DEVICE double[n], weights of any sign, or NULL: all 1.  d = the minimum-image difference
+ * x_j - x_i of the wrapped coordinates exactly as fb_fof_link and fb_pair_count take it, d^2 = (dx dx + dy dy) + dz dz with every
+ * operation rounded on its own.  Particle j != i -- by index, not by position -- is in bin b of primary i iff edges2[b] <= d^2 <
+ * edges2[b + 1]; edges2: HOST double[nr + 1], the squares of the edges, strictly ascending from > 0, so that a particle with
+ * d^2 < edges2[0], a coincident one included, is in no bin and no direction of a zero vector is formed.  The unit vector is
+ * (x, y, z) = d / sqrt(d^2), component by component.  Real orthonormal harmonics by this recurrence (+ - x / sqrt only):
+ *   c_0 = 1, s_0 = 0, c_m = x c_(m-1) - y s_(m-1), s_m = x s_(m-1) + y c_(m-1);
+ *   A_0 = sqrt(1 / (4 pi)), A_m = A_(m-1) sqrt((2 m + 1) / (2 m)); Q_m^m = A_m; Q_(m+1)^m = (sqrt(2 m + 3) z) Q_m^m;
+ *   Q_l^m = alpha_lm (z Q_(l-1)^m - beta_lm Q_(l-2)^m), alpha_lm = sqrt((4 l^2 - 1) / (l^2 - m^2)),
+ *   beta_lm = sqrt(((l - 1)^2 - m^2) / (4 (l - 1)^2 - 1));
+ *   Y_l0 = Q_l^0, Y_l,+m = (sqrt(2) Q_l^m) c_m, Y_l,-m = (sqrt(2) Q_l^m) s_m; index lm = l^2 + l + m.
+ * The constants are formed once on the host in fp64.  Per primary i and bin b: a_lm(b) = sum_j w_j Y_lm, N(b) = #{j in b},
+ * S(b) = sum_j w_j^2, and
+ *   M_l(b1, b2) = sum_i w_i ((4 pi / (2 l + 1)) sum_m a_lm(b1) a_lm(b2) - [b1 = b2] S(b1)),
+ * the sum over m in ascending order in fp64 -- by the addition theorem the sum over ordered triplets (i; j != k) of
+ * w_i w_j w_k P_l(u_ij . u_ik).  Every sum over particles is fixed-point in two 64-bit words with F = 93 - e fractional bits,
+ * bound < 2^e (frexp), the bound being 2 n wmax for the a_lm, n wmax^2 for S and 4 (n wmax)^3 for M, wmax = max |w| (1 without
+ * weights): the same bit for bit from call to call and for any order of the particles.
+ * Limits: 0 <= n <= 2^31 - 2, 1 <= nr <= 32, 0 <= lmax <= 10 (lmax = 10 with nr = 32 takes 149 KiB of the CU's LDS).  ncell:
+ * HOST int[3], cells per axis, at least 2 and of side L_a / ncell_a >= sqrt(edges2[nr]), which must stay below L_a / 2 (the
+ * caller leaves the margin for the rounding of a cell index: pair_cells of halos.py).
+ * fb_triplet_work_bytes: bytes of the work buffer (-1: bad arguments): 32 n bytes, 8 n more with weights, 8 bytes per cell and
+ *   8 KiB x (lmax + 1) nr (nr + 1) / 2 for the workgroups' partial sums.
+ * fb_triplet_multipoles: M_out (DEVICE double[lmax + 1][nr][nr], symmetric in the bins); pairs_out (DEVICE uint64[nr]) =
+ *   sum_i N_i(b), the ordered pairs of fb_pair_count's auto-counts.  probe_idx: HOST int32[nprobe], nprobe <= 64 (0: none): the
+ *   a_lm of these primaries, given by their index in pos, go to alm_out (DEVICE double[nprobe][(lmax + 1)^2][nr]).  *bad = 1
+ *   (and all outputs zero) if a position is not finite or has |x| >= 2^52 L; *bad = 4 if a weight, or 4 (n wmax)^3, is not
+ *   finite.  stage_ms: HOST double[3] or NULL: milliseconds of the binning, the sweep and the finish.  Synchronises.         */
+int64_t fb_triplet_work_bytes(int64_t n, int64_t ncells, int nr, int lmax, int weighted);
+int fb_triplet_multipoles(fb_plan* plan, const double* pos, const double* w, int64_t n, const int* ncell, const double* edges2,
+                          int nr, int lmax, void* work, int64_t work_bytes, double* M_out, uint64_t* pairs_out,
+                          const int32_t* probe_idx, int nprobe, double* alm_out, int* bad, double* stage_ms, void* stream);
+
 /* ---- transfer functions (apply_transfer_fn box.py:374-379, smooth_field :651-653) ---------- */
 #define FB_FILT_TABLE 0          /* table: real multiplier, same layout as the field */
 #define FB_FILT_BEAM_HIGHPASS 1  /* (1-exp(-.5(|kpar|/p0)^p2)) [p0>0] * exp(-.5(kperp/p1)^2) [p1>0] */
